@@ -3,14 +3,21 @@
 (ConvNeXt-base, 512x512, batch 32 per GPU, default head, masked SmoothL1) on synthetic uint8
 images normalised like the reference's transforms, inputs already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps, the result
+line.  ``--dump-outputs DIR`` also writes what the last timed step computed as ``DIR/<name>.npy`` (float32): the
+returned loss, the gradient norm and a fixed, seeded sample of the updated parameters (or, with ``--inference``, the
+forward's outputs); with the same arguments the inputs are identical from run to run.  ``--full`` adds everything else
+described below: the per-kernel probes and rooflines, the main-queue busy time, the data-parallel rehearsal, the
+classification line and the CPU baselines.
 
 N > 1: when launched without torch.distributed.run (no WORLD_SIZE in the environment) bench.py starts
 ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1`` on itself as a CHILD
 process before touching the GPU, and exits with its code; launched by torch.distributed.run it is one
 rank (RANK / LOCAL_RANK / WORLD_SIZE from the environment; rank 0 checks WORLD_SIZE == --gpus).
 
-Rank 0 prints ONE JSON line.  ``roofline`` is the dominant GEMM class of the step (the one with the
+Rank 0 prints ONE JSON line.  With ``--full``, ``roofline`` is the dominant GEMM class of the step (the one with the
 most device time): every launch of each probed class is timed with HIP events on its launching
 stream in the last timed step; ``roofline.kernels`` carries every probed class (split-K weight
 gradients, the fc2 data gradient, the forward GEMMs) and ``step_mfma_frac`` the whole-step model-FLOP
@@ -104,7 +111,12 @@ def parse():
     ap.add_argument("--selftest", action="store_true",
                     help="launcher / all-reduce plumbing check on CPU (gloo, a small torch model): no GPU, no "
                          "measurement -- used by tests/test_bench_launcher.py")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel probes and rooflines, the "
+                         "main-queue busy time, the data-parallel rehearsal, the classification line, CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baselines out")
     ap.add_argument("--inference", action="store_true",
                     help="secondary line (row f2): the validation / predict forward (eval mode, no tape) instead "
                          "of the training step")
@@ -285,7 +297,7 @@ def classification_line(args) -> dict:
     after the headline's timed region; its JSON line is condensed here.  SV_BENCH_CLS=0 skips it."""
     steps, warmup = max(args.steps, 20), max(args.warmup, 5)
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "classification", "--steps", str(steps),
-           "--warmup", str(warmup), "--no-cpu-baseline", "--precision", args.precision]
+           "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--precision", args.precision]
     env = dict(os.environ, SV_BENCH_CLS="0")
     t0 = time.perf_counter()
     try:
@@ -549,6 +561,34 @@ def step_floor(kern: dict, ms: float, peak: float) -> dict:
                     "classes_ms_per_step adds their in-step durations, which overlap across the two streams"}
 
 
+DUMP_PARAM_SAMPLE = 1 << 20  # parameters kept of the flat buffer (4 MB as float32)
+
+
+def dump_outputs(path: str, engine, loss, fwd_out) -> None:
+    """--dump-outputs: what the last timed step handed back, as ``path/<name>.npy`` (float32).  Training: the returned
+    loss, the global gradient norm the clip measured, and the updated parameters at DUMP_PARAM_SAMPLE fixed positions of
+    the flat buffer (drawn once with a seeded CPU generator, sorted).  --inference: the forward's outputs."""
+    import numpy as np
+
+    def arr(t):
+        return t.detach().float().cpu().numpy().astype(np.float32)
+
+    os.makedirs(path, exist_ok=True)
+    if fwd_out is not None:
+        outs = {f"pred_{k}": v for k, v in fwd_out.items()} if isinstance(fwd_out, dict) else {"pred": fwd_out}
+    else:
+        flat = engine.arena.param_flat
+        n = flat.numel()
+        if n > DUMP_PARAM_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(2024))
+            flat = flat[idx.sort().values.to(flat.device)]
+        outs = {"loss": loss.reshape(1), "params_sample": flat}
+        if engine.last_grad_norm is not None:
+            outs["grad_norm"] = engine.last_grad_norm.reshape(1)
+    for name, t in outs.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr(t))
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -606,12 +646,14 @@ def main():
         def run_step():
             return engine.step_localization(img, coords, mask)
 
+    fwd_out: dict = {}
     if args.inference:  # row f2: trainers' _validate_epoch / predict forward, no autograd tape
         model.eval()
 
         def run_step():  # noqa: F811
             with torch.no_grad():
                 out = model(img)
+            fwd_out["out"] = out
             return out.float().mean() if not isinstance(out, dict) else sum(v.float().mean() for v in out.values())
 
     for _ in range(args.warmup):
@@ -631,13 +673,13 @@ def main():
     # (tools/gpu_probe_ab.sh).  The classification line reports the whole-step rate and takes no probe;
     # SV_BENCH_PROBE=0 leaves the per-kernel fields empty and SV_BENCH_PROBE=all probes every step.
     probe_mode = os.environ.get("SV_BENCH_PROBE", "1")
-    use_probe = not cls and not args.inference and probe_mode != "0"
+    use_probe = args.full and not cls and not args.inference and probe_mode != "0"
     bucketer = engine.bucketer
     # world 1: rehearse the data-parallel exchange -- when each 64 MB bucket's gradients become final in
     # the last timed step, and a prediction of the exposed all-reduce at N ranks (comm.BucketTimeline)
     timeline = None
     tl_ev: dict = {}
-    if world == 1 and not args.inference and os.environ.get("SV_BENCH_TIMELINE", "1") != "0":
+    if args.full and world == 1 and not args.inference and os.environ.get("SV_BENCH_TIMELINE", "1") != "0":
         from spine_vision_amd.training.comm import BucketTimeline
 
         timeline = BucketTimeline(engine.arena, model, bucket_mb=64.0)
@@ -680,8 +722,10 @@ def main():
     # the main queue's busy time: the critical path of the two-stream backward is the stream the
     # step runs on, not the dominant-by-time side-stream class.  One extra, untimed step with HIP events around every
     # sv_* launch on that stream (torch's own kernels there -- head, loss -- are not bracketed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, loss, fwd_out.get("out"))
     main_queue = None
-    if not args.inference and os.environ.get("SV_BENCH_MAINQ", "1") != "0":
+    if args.full and not args.inference and os.environ.get("SV_BENCH_MAINQ", "1") != "0":
         mstream = engine._stream if getattr(engine, "_stream", None) is not None else torch.cuda.current_stream()
         nv.STREAM_PROBE = nv.StreamProbe(mstream)
         try:
@@ -825,10 +869,10 @@ def main():
                                  latency_samples_ms=samples[0], hbm_gbs=HBM_SUSTAINED_GBS) for bw in (200.0, 300.0, 400.0)]
     if world > 1:
         result["config"]["comm_reserve_cus"] = engine.comm_reserve_cus
-    if (rank == 0 and world == 1 and not cls and not args.inference and args.backbone == "convnext_base"
+    if (args.full and rank == 0 and world == 1 and not cls and not args.inference and args.backbone == "convnext_base"
             and os.environ.get("SV_BENCH_CLS", "1") != "0"):
         result["configs3_classification"] = classification_line(args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args)
         if not cls and not args.inference:
             result["cpu_baseline_configs0"] = cpu_baseline_config0()

@@ -60,17 +60,41 @@ def _worker(rank, world, port, tmp, q):
     dist.destroy_process_group()
 
 
-def test_validation_and_scheduler_gloo_world2(tmp_path):
+def _collect(q, procs, n, limit=180.0):
+    """n results from the queue; a worker that died without reporting fails the test at once."""
+    import queue
+    import time
+
+    res, t0 = [], time.monotonic()
+    while len(res) < n:
+        try:
+            res.append(q.get(timeout=0.5))
+        except queue.Empty:
+            dead = [p.exitcode for p in procs if p.exitcode not in (None, 0)]
+            assert not dead, f"worker exit codes {dead}"
+            assert time.monotonic() - t0 < limit, "workers did not report"
+    return res
+
+
+def test_validation_and_scheduler_gloo_world2(tmp_path, monkeypatch):
     world, port = 2, _free_port()
+    # host logic on the CPU path: the spawned workers see no GPU (with one, the trainer would put rank r on cuda:r)
+    for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        monkeypatch.setenv(var, "-1")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_worker, args=(r, world, port, str(tmp_path / f"r{r}"), q)) for r in range(world)]
     for p in procs:
         p.start()
-    res = sorted(q.get(timeout=180) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    try:
+        res = sorted(_collect(q, procs, world))
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
     # 10 val samples, bs 4, world 2: unsharded batches [4,4,2] -> 2 full batches per rank (padded)
     for rank, w, tmax, nvb, nrows, metrics in res:
         assert w == 2

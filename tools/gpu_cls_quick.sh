@@ -10,7 +10,7 @@ rc=$?; echo "tests rc=$rc $(tail -1 $OUT/tests.log)"
 timeout -k 10 120 python tools/conv_bench.py > "$OUT/conv.txt" 2>&1 || exit $?
 cat "$OUT/conv.txt" | grep -v amdgpu
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --workload classification --steps 30 --warmup 5 --no-cpu-baseline > "$OUT/bench_$r.json" 2> "$OUT/bench_$r.err"
+  timeout -k 10 300 python bench.py --workload classification --steps 30 --warmup 5 --full --no-cpu-baseline > "$OUT/bench_$r.json" 2> "$OUT/bench_$r.err"
   rc=$?; echo "r=$r rc=$rc $(python3 -c "import json; d=json.load(open('$OUT/bench_$r.json')); print(d['value'], d['ms_per_step'])" 2>&1 | tail -1)"
   [ $rc -ne 0 ] && exit $rc
 done

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-cfg}
 mkdir -p "$OUT"
 run() {
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" --no-cpu-baseline > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout -k 10 400 python bench.py "$@" --full --no-cpu-baseline > "$OUT/$name.json" 2> "$OUT/$name.err"
   local rc=$?
   echo "$name rc=$rc $(head -c 200 "$OUT/$name.json" | sed 's/.*"value": \([0-9.]*\).*/\1/')"
   [ $rc -ne 0 ] && exit $rc

@@ -11,7 +11,7 @@ timeout -k 10 300 python tools/dw_bench.py > "$OUT/dw.txt" 2>&1
 rc=$?; echo "dw rc=$rc"; grep -v amdgpu "$OUT/dw.txt"
 [ $rc -ne 0 ] && exit $rc
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench$i.json" 2> "$OUT/bench$i.err"
+  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > "$OUT/bench$i.json" 2> "$OUT/bench$i.err"
   rc=$?; echo "bench rc=$rc $(python3 -c "import json; d=json.load(open('$OUT/bench$i.json')); print(d['value'], d['ms_per_step'])")"
   [ $rc -ne 0 ] && exit $rc
 done

@@ -11,7 +11,7 @@ timeout -k 10 400 python -u tools/gemm_bench.py --stages ${STAGES:-S1,S2,S3,S4} 
 rc=$?; echo "gemm rc=$rc"; grep -v torch "$OUT/gemm.txt"
 [ $rc -ne 0 ] && exit $rc
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench$i.json" 2> "$OUT/bench$i.err"
+  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > "$OUT/bench$i.json" 2> "$OUT/bench$i.err"
   rc=$?; echo "bench rc=$rc $(python3 -c "import json; d=json.load(open('$OUT/bench$i.json')); print(d['value'], d['ms_per_step'])")"
   [ $rc -ne 0 ] && exit $rc
 done

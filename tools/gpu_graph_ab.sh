@@ -9,7 +9,7 @@ rc=$?; echo "tests rc=$rc $(tail -1 $OUT/tests.log)"
 [ $rc -ne 0 ] && { grep -E "^FAILED|Error|assert" "$OUT/tests.log" | head -20; exit $rc; }
 for r in 1 2; do
   for gr in on off; do
-    timeout -k 10 300 python bench.py --workload classification --steps 30 --warmup 5 --no-cpu-baseline --graph $gr > "$OUT/bench_${gr}_$r.json" 2> "$OUT/bench_${gr}_$r.err"
+    timeout -k 10 300 python bench.py --workload classification --steps 30 --warmup 5 --full --no-cpu-baseline --graph $gr > "$OUT/bench_${gr}_$r.json" 2> "$OUT/bench_${gr}_$r.err"
     rc=$?; echo "graph=$gr r=$r rc=$rc $(python -c "import json; d=json.load(open('$OUT/bench_${gr}_$r.json')); print(d['value'], d['ms_per_step'], d['config']['hip_graph'])" 2>&1)"
     [ $rc -ne 0 ] && { tail -5 "$OUT/bench_${gr}_$r.err"; exit $rc; }
   done

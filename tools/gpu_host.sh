@@ -13,7 +13,7 @@ for w in classification localization; do
   timeout -k 10 300 python tools/host_time.py --workload $w > "$OUT/host_$w.log" 2>&1
   rc=$?; echo "host $w rc=$rc $(grep host "$OUT/host_$w.log" | tail -1)"
   [ $rc -ne 0 ] && exit $rc
-  timeout -k 10 300 python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+  timeout -k 10 300 python bench.py --workload $w --steps 10 --warmup 3 --full --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
   rc=$?; echo "bench $w rc=$rc $(head -c 200 "$OUT/bench_$w.json" | sed 's/.*"value": \([0-9.]*\).*/\1/')"
   [ $rc -ne 0 ] && exit $rc
 done

@@ -11,7 +11,7 @@ if [ -n "${TESTS:-}" ]; then
 fi
 for rep in 1 2; do
   for v in 1 0; do
-    SV_LEAN_SYNC=$v timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/l${v}_$rep.json" 2> "$OUT/l${v}_$rep.err"
+    SV_LEAN_SYNC=$v timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > "$OUT/l${v}_$rep.json" 2> "$OUT/l${v}_$rep.err"
     rc=$?; echo "lean=$v rep=$rep rc=$rc $(python -c "import json;b=json.load(open('$OUT/l${v}_$rep.json'));print(b['value'], b.get('hbm_reserved_gb'))")"
     [ $rc -ne 0 ] && exit $rc
   done

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 while read -r name ctrs; do
   [ -z "$name" ] && continue
-  timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$ROOTDIR/$OUT/pmc_$name" -o run -- python3 "$ROOTDIR/bench.py" --steps 2 --warmup 1 --no-cpu-baseline $BENCH_ARGS > "$ROOTDIR/$OUT/pmc_$name.log" 2>&1
+  timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$ROOTDIR/$OUT/pmc_$name" -o run -- python3 "$ROOTDIR/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline $BENCH_ARGS > "$ROOTDIR/$OUT/pmc_$name.log" 2>&1
   rc=$?; echo "pmc $name rc=$rc"
   [ $rc -ne 0 ] && exit $rc
 done <<< "FETCH_SIZE FETCH_SIZE
