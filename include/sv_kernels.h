@@ -238,6 +238,34 @@ int sv_layernorm_bwd(const void* dy, int32_t dy_dtype, const void* x, int32_t x_
                      const float* rstd, const float* w, void* dx, int32_t dx_dtype, int32_t accumulate,
                      float* dw_part, float* db_part, int64_t rows, int32_t C, sv_stream_t stream);
 
+/* ---- Global Response Normalization (ConvNeXt V2) ----------------------------------------------
+ * Replaces timm GlobalResponseNorm (channels-last, eps 1e-6) between GELU and fc2 of a V2 block, over the hidden
+ * activation a = GELU(h), a [B*HW][n] matrix (n = 4C, n % 8 == 0, `dtype` f32 or bf16 for every activation of a call):
+ *   G[b,c] = sqrt(sum_p a^2),  D[b] = mean_c G + eps,  N = G / D,  u = a (1 + gamma[c] N[b,c]) + beta[c].
+ * forward:  sv_grn_stats writes the per-chunk sums of a^2 to part [B][P][n], P = sv_grn_nparts(HW, n) chunks of
+ *           consecutive pixels per image; sv_grn_finish folds them in chunk order and writes G, N and
+ *           scale = 1 + gamma N as [B][n] and D as [B]; sv_grn_apply writes u = a scale + beta (u may be a).
+ * backward: from du = dL/du, sv_grn_bwd_stats writes the per-chunk sums of du a and du to s_part / d_part
+ *           [B][P][n]; sv_grn_bwd_finish folds them (the per-image totals are left in chunk 0 of both buffers),
+ *           writes k = dG / G [B][n] (0 where G == 0; dG = gamma S / D - (sum_c gamma S G) / (n D^2)) and writes
+ *           (accumulate = 0) or adds (1) dgamma[c] = sum_b S N, dbeta[c] = sum_{b,p} du, images in order;
+ *           sv_grn_bwd_apply writes dh = (du scale + a k) gh with gh = GELU'(h) (dh may be du).
+ * Every activation, partial and [B][n] pointer must be 16-byte aligned.  No atomics: results are bitwise
+ * reproducible run to run.                                                                                       */
+int sv_grn_nparts(int64_t HW, int32_t n);
+int sv_grn_stats(const void* a, int32_t dtype, float* part, int32_t B, int64_t HW, int32_t n, sv_stream_t stream);
+int sv_grn_finish(const float* part, int32_t nparts, const float* gamma, float* G, float* N, float* scale, float* D,
+                  int32_t B, int32_t n, float eps, sv_stream_t stream);
+int sv_grn_apply(const void* a, int32_t dtype, const float* scale, const float* beta, void* u, int32_t B, int64_t HW,
+                 int32_t n, sv_stream_t stream);
+int sv_grn_bwd_stats(const void* du, const void* a, int32_t dtype, float* s_part, float* d_part, int32_t B,
+                     int64_t HW, int32_t n, sv_stream_t stream);
+int sv_grn_bwd_finish(float* s_part, float* d_part, int32_t nparts, const float* gamma, const float* G,
+                      const float* N, const float* D, float* k, float* dgamma, float* dbeta, int32_t accumulate,
+                      int32_t B, int32_t n, sv_stream_t stream);
+int sv_grn_bwd_apply(const void* du, const void* a, const void* gh, int32_t dtype, const float* scale, const float* k,
+                     void* dh, int32_t B, int64_t HW, int32_t n, sv_stream_t stream);
+
 /* ---- ConvNeXt block head: depthwise 7x7 (pad 3, bias) fused with the channels-last LayerNorm --
  * Replaces ConvNeXtBlock.conv_dw + permute + ConvNeXtBlock.norm (timm convnext.py).
  * x [B,H,W,C] (x_dtype), wdw [C][49] (timm weight [C,1,7,7]), bdw [C].

@@ -15,6 +15,14 @@ spine_vision/training/models/backbone.py:166-170 (timm 1.0.22 ``timm/models/conv
 * ``precision="bf16"``: bf16 MFMA, bf16 saved activations, f32 residual/gradient streams, f32
   master weights.  ``precision="fp32"``: every tensor f32 and f32 MFMA (parity mode, <=1e-3 vs the
   reference CPU path).
+* ConvNeXt V2 (``convnextv2_{base,large}``, timm's Linear-MLP V2 variants): a block has no layer-scale ``gamma``
+  and puts Global Response Normalization between GELU and fc2 -- ``mlp.grn.{weight,bias}`` ([4C], zeros at init).
+  The state_dict keys are V1's minus ``gamma`` plus those two.  timm is not a dependency of this package, so this is an
+  assumption, stated here: the key names and the arithmetic (``u = a + bias + weight * a * N``, ``N = G / (mean_c G + 1e-6)``, ``G`` the L2 norm
+  of ``a`` over an image's pixels) are timm 1.0.22's ``GlobalResponseNormMlp`` / ``GlobalResponseNorm`` as
+  published, checked against HF transformers' ``ConvNextV2Model`` through a key remap (tests/test_convnextv2_cpu.py).
+  GRN runs as its own HBM-bound passes (csrc/grn.hip; DESIGN.md "ConvNeXt V2"), so V2 blocks never take the fused
+  MLP kernels, which fuse across the point where GRN sits.
 """
 
 from __future__ import annotations
@@ -35,6 +43,8 @@ CONVNEXT_CFGS = {
     "convnext_small": ((3, 3, 27, 3), (96, 192, 384, 768)),
     "convnext_base": ((3, 3, 27, 3), (128, 256, 512, 1024)),
     "convnext_large": ((3, 3, 27, 3), (192, 384, 768, 1536)),
+    "convnextv2_base": ((3, 3, 27, 3), (128, 256, 512, 1024)),
+    "convnextv2_large": ((3, 3, 27, 3), (192, 384, 768, 1536)),
 }
 
 
@@ -63,14 +73,41 @@ class ConvNeXtBlock(nn.Module):
         self.gamma = nn.Parameter(ls_init_value * torch.ones(dim))
 
 
+class _Grn(nn.Module):
+    """Parameter container for timm GlobalResponseNorm (channels-last): weight and bias [dim], zeros at init."""
+
+    def __init__(self, dim: int) -> None:
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(dim))
+        self.bias = nn.Parameter(torch.zeros(dim))
+
+
+class _GrnMlp(nn.Module):
+    def __init__(self, dim: int, hidden: int) -> None:
+        super().__init__()
+        self.fc1 = nn.Linear(dim, hidden)
+        self.grn = _Grn(hidden)
+        self.fc2 = nn.Linear(hidden, dim)
+
+
+class ConvNeXtV2Block(nn.Module):
+    """Parameter container for timm ConvNeXtBlock(conv_mlp=False, use_grn=True, ls_init_value=None): no ``gamma``."""
+
+    def __init__(self, dim: int) -> None:
+        super().__init__()
+        self.conv_dw = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim, bias=True)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.mlp = _GrnMlp(dim, 4 * dim)
+
+
 class ConvNeXtStage(nn.Module):
-    def __init__(self, in_chs: int, out_chs: int, depth: int, downsample: bool) -> None:
+    def __init__(self, in_chs: int, out_chs: int, depth: int, downsample: bool, block=ConvNeXtBlock) -> None:
         super().__init__()
         if downsample:
             self.downsample = nn.Sequential(nn.LayerNorm(in_chs, eps=1e-6), nn.Conv2d(in_chs, out_chs, 2, stride=2))
         else:
             self.downsample = nn.Identity()
-        self.blocks = nn.Sequential(*[ConvNeXtBlock(out_chs) for _ in range(depth)])
+        self.blocks = nn.Sequential(*[block(out_chs) for _ in range(depth)])
 
 
 class _Head(nn.Module):
@@ -120,19 +157,25 @@ _TAIL_MAIN = int(os.environ.get("SV_TAIL_MAIN", "0"))
 
 class ConvNeXtHip(nn.Module):
     def __init__(self, depths=(3, 3, 27, 3), dims=(128, 256, 512, 1024), ls_init_value: float = 1e-6,
-                 precision: str = "bf16") -> None:
+                 precision: str = "bf16", use_grn: bool = False) -> None:
         super().__init__()
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
         self.depths, self.dims = tuple(depths), tuple(dims)
         self.precision = precision
+        self.use_grn = bool(use_grn)  # ConvNeXt V2 blocks: GRN between GELU and fc2, no layer scale
         self.stem = nn.Sequential(nn.Conv2d(3, dims[0], kernel_size=4, stride=4), nn.LayerNorm(dims[0], eps=1e-6))
         stages = []
         prev = dims[0]
         for i, (d, c) in enumerate(zip(depths, dims)):
-            stages.append(ConvNeXtStage(prev, c, d, downsample=i > 0))
+            stages.append(ConvNeXtStage(prev, c, d, downsample=i > 0,
+                                        block=ConvNeXtV2Block if self.use_grn else ConvNeXtBlock))
             prev = c
         self.stages = nn.Sequential(*stages)
+        if self.use_grn:
+            # fc2's bias + residual epilogue (SV_EPI_BIAS_GAMMA_RES) with a layer scale of exactly one: V2 has none.
+            # Not persistent: it stays out of the state_dict
+            self.register_buffer("ls_ones", torch.ones(max(dims)), persistent=False)
         self.norm_pre = nn.Identity()
         self.head = _Head(prev)
         self.num_features = self.head_hidden_size = prev
@@ -262,7 +305,8 @@ class ConvNeXtHip(nn.Module):
         gate = self.param_gate
         if gate is not None:
             gate.wait(self.stem)
-        if save and bf and self.overlap_wgrad:
+        if save and bf and self.overlap_wgrad and not self.use_grn:
+            # (not V2: its blocks have no gamma, and their fc2 data gradient reads the plain bf16 W2)
             # the fc2 dgrad operand bf16(W2 * gamma) of every block, made on the (otherwise idle during
             # the forward) side stream beside the forward; the backward waits on one event
             # (allocated on the main stream, which frees them after waiting on w2g_ready: no
@@ -330,7 +374,7 @@ class ConvNeXtHip(nn.Module):
                                                     blk.norm.bias, act_dtype=act, save_z=save)
                 w1 = self._w(blk.mlp.fc1.weight, cache)
                 w2 = self._w(blk.mlp.fc2.weight, cache)
-                if bf and self.fused_mlp and C in K.MLP_FUSED_C and C in self.fused_mlp_c:
+                if bf and self.fused_mlp and not self.use_grn and C in K.MLP_FUSED_C and C in self.fused_mlp_c:
                     # fused MLP: the training forward stores GELU'(h) and GELU(h) for the backward, the eval one nothing
                     xo = torch.empty(B, H, W, C, device=x.device, dtype=torch.float32)
                     gh = torch.empty(M, 4 * C, device=x.device, dtype=act) if save else None
@@ -338,7 +382,7 @@ class ConvNeXtHip(nn.Module):
                     K.mlp_fwd(y, w1, blk.mlp.fc1.bias, w2, blk.mlp.fc2.bias, blk.gamma, x.view(M, C), out=xo.view(M, C),
                               gelu_grad=gh, gelu_out=a)
                     if save:
-                        blocks_saved.append((x, z, y, mean, rstd, gh, a))
+                        blocks_saved.append((x, z, y, mean, rstd, gh, a, None))
                     x = xo
                     continue
                 # fc1 epilogue: a = GELU(h) (fc2 operand) and gh = GELU'(h) (for the backward), one erf;
@@ -353,10 +397,21 @@ class ConvNeXtHip(nn.Module):
                     K.linear_fwd(y, w1, out=a, bias=blk.mlp.fc1.bias, epilogue=nv.SV_EPI_BIAS_GELU,
                                  compute_bf16=bf)
                 xo = torch.empty(B, H, W, C, device=x.device, dtype=torch.float32)
-                K.linear_fwd(a, w2, out=xo.view(M, C), bias=blk.mlp.fc2.bias, gamma=blk.gamma,
-                             residual=x.view(M, C), epilogue=nv.SV_EPI_BIAS_GAMMA_RES, compute_bf16=bf)
+                grn_saved = None
+                if self.use_grn:
+                    # V2: u = a (1 + gamma N) + beta from the per-image channel norms of a (stats, finish, apply);
+                    # training keeps a (the GRN backward reads it) and u (the fc2 weight gradient's operand), the
+                    # tape-free forward overwrites a
+                    grn = blk.mlp.grn
+                    u, gst = K.grn_fwd(a, B, grn.weight, grn.bias, inplace=not save)
+                    grn_saved = (u, gst)
+                    K.linear_fwd(u, w2, out=xo.view(M, C), bias=blk.mlp.fc2.bias, gamma=self.ls_ones[:C],
+                                 residual=x.view(M, C), epilogue=nv.SV_EPI_BIAS_GAMMA_RES, compute_bf16=bf)
+                else:
+                    K.linear_fwd(a, w2, out=xo.view(M, C), bias=blk.mlp.fc2.bias, gamma=blk.gamma,
+                                 residual=x.view(M, C), epilogue=nv.SV_EPI_BIAS_GAMMA_RES, compute_bf16=bf)
                 if save:
-                    blocks_saved.append((x, z, y, mean, rstd, gh, a))
+                    blocks_saved.append((x, z, y, mean, rstd, gh, a, grn_saved))
                 x = xo
             if save:
                 tape.stages.append((ds_saved, blocks_saved))
@@ -377,7 +432,7 @@ class ConvNeXtHip(nn.Module):
     def _fused_bwd(self, blk) -> bool:
         """Whether this block's backward runs the fused fc2 -> fc1 -> LayerNorm data-gradient kernel (bf16 lean
         side-stream schedule only: its operand images are made beside the forward)."""
-        return (self.fused_mlp_bwd and self.compute_bf16 and self.overlap_wgrad and self.lean_sync
+        return (self.fused_mlp_bwd and not self.use_grn and self.compute_bf16 and self.overlap_wgrad and self.lean_sync
                 and blk.conv_dw.weight.shape[0] in K.MLP_BWD_FUSED_C)
 
     def _side_stream(self, device) -> torch.cuda.Stream:
@@ -402,6 +457,23 @@ class ConvNeXtHip(nn.Module):
     def _ready(self, params: list) -> None:
         if self.grad_ready_hook is not None:
             self.grad_ready_hook(params)
+
+    def _fc2_params(self, blk) -> list:
+        """The parameters whose gradients the fc2 stage of a block's backward writes."""
+        if self.use_grn:
+            return [blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.mlp.grn.weight, blk.mlp.grn.bias]
+        return [blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.gamma]
+
+    def _grn_dgrad(self, blk, dsrc, a, gh, grn_saved, dh, cache, pol) -> None:
+        """V2 fc2 stage of the data-gradient chain: du = d W2 (plain store) into ``dh``, then the GRN backward
+        (stats, finish, apply) in place, dh = (du (1 + gamma N) + a k) GELU'(h); the GRN weight / bias gradients are
+        added on this stream."""
+        bf = self.compute_bf16
+        w2 = self._w(blk.mlp.fc2.weight, cache) if bf else blk.mlp.fc2.weight.detach()
+        K.linear_dgrad(dsrc, w2, out=dh, compute_bf16=bf, policy=pol)
+        grn, gst = blk.mlp.grn, grn_saved[1]
+        K.grn_bwd(dh, a, gh, gst[0].shape[0], grn.weight, gst, dgamma=self._grad(grn.weight),
+                  dbeta=self._grad(grn.bias))
 
     @torch.no_grad()
     def _backward_impl(self, tape: _Tape, dfeat: torch.Tensor) -> None:
@@ -436,7 +508,7 @@ class ConvNeXtHip(nn.Module):
                 # the tape lets go of the block: its main-stream reads are stream-ordered before any
                 # later main-stream allocation, its side-stream reads stay referenced below
                 blocks_saved[bi] = None
-                x, z, y, mean, rstd, gh, a = saved
+                x, z, y, mean, rstd, gh, a, grn_saved = saved
                 B, H, W, C = x.shape
                 M = B * H * W
                 d2 = d.view(M, C)
@@ -457,18 +529,25 @@ class ConvNeXtHip(nn.Module):
                 # with small outputs, the dgrads epilogue/HBM-bound, so the two overlap on the chip
                 if side is not None:
                     side.wait_event(main.record_event())
-                    for t_ in (dsrc, a):
+                    for t_ in (dsrc, grn_saved[0] if self.use_grn else a):
                         t_.record_stream(side)
                 with torch.cuda.stream(side) if side is not None else _nullctx():
-                    # dW2 = gamma (.) d^T a, dgamma = rowdot(W2, d^T a) + b2 (.) colsum(d), db2 = gamma (.) colsum(d)
-                    K.layerscale_wgrad(dsrc, a, blk.mlp.fc2.weight.detach(), blk.gamma.detach(),
-                                       blk.mlp.fc2.bias.detach(), dw2=g(blk.mlp.fc2.weight), dgamma=g(blk.gamma),
-                                       db2=g(blk.mlp.fc2.bias), compute_bf16=bf, policy=pol)
+                    if self.use_grn:
+                        # V2 (no layer scale): dW2 = d^T u, db2 = colsum(d), u the GRN output fc2 read
+                        K.linear_wgrad(dsrc, grn_saved[0], out=g(blk.mlp.fc2.weight), accumulate=True,
+                                       bias_out=g(blk.mlp.fc2.bias), compute_bf16=bf, policy=pol)
+                    else:
+                        # dW2 = gamma (.) d^T a, dgamma = rowdot(W2, d^T a) + b2 (.) colsum(d), db2 = gamma (.) colsum(d)
+                        K.layerscale_wgrad(dsrc, a, blk.mlp.fc2.weight.detach(), blk.gamma.detach(),
+                                           blk.mlp.fc2.bias.detach(), dw2=g(blk.mlp.fc2.weight), dgamma=g(blk.gamma),
+                                           db2=g(blk.mlp.fc2.bias), compute_bf16=bf, policy=pol)
                 ev_w2 = side.record_event() if side is not None else None
                 # fc2: dh = ((d * gamma) @ W2) * GELU'(h).  bf16 mode folds gamma into a bf16 copy of W2;
                 # GELU'(h) was stored by the forward epilogue
                 dh = torch.empty(M, 4 * C, device=d.device, dtype=act)
-                if bf:
+                if self.use_grn:
+                    self._grn_dgrad(blk, dsrc, a, gh, grn_saved, dh, cache, pol)
+                elif bf:
                     w2g = tape.w2g.pop(id(blk), None)
                     if w2g is None:
                         w2g = K.scale_rows_bf16(blk.mlp.fc2.weight.detach(), blk.gamma.detach())
@@ -503,7 +582,7 @@ class ConvNeXtHip(nn.Module):
                                                     defer_reduce=True)
                 dz4 = dz.view(B, H, W, C)
                 blk_params = [blk.conv_dw.weight, blk.conv_dw.bias, blk.norm.weight, blk.norm.bias,
-                              blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.gamma]
+                              blk.mlp.fc1.weight, blk.mlp.fc1.bias, *self._fc2_params(blk)]
                 if side is not None:
                     side.wait_event(main.record_event())
                     for t_ in (dz, x):
@@ -590,7 +669,7 @@ class ConvNeXtHip(nn.Module):
         it, r11k trace); only the fc2 one goes there, and the fc1 and depthwise ones (with the block's fold) are
         appended to ``tail`` for the main stream to run after the stem."""
         g = self._grad
-        x, z, y, mean, rstd, gh, a = saved
+        x, z, y, mean, rstd, gh, a, grn_saved = saved
         B, H, W, C = x.shape
         M = B * H * W
         wt = tape.wt.pop(id(blk), None)
@@ -608,10 +687,13 @@ class ConvNeXtHip(nn.Module):
                     K.reduce_pair(_p[0], dw_ln, _p[1], db_ln, _n)
         else:
             w1 = self._w(blk.mlp.fc1.weight, cache)
-            w2g = tape.w2g.pop(id(blk), None)
-            if w2g is None:
-                w2g = K.scale_rows_bf16(blk.mlp.fc2.weight.detach(), blk.gamma.detach())
-            K.linear_dgrad(dsrc, w2g, out=dh, epilogue=nv.SV_EPI_MUL_AUX, aux=gh, compute_bf16=True, policy=pol)
+            if self.use_grn:
+                self._grn_dgrad(blk, dsrc, a, gh, grn_saved, dh, cache, pol)
+            else:
+                w2g = tape.w2g.pop(id(blk), None)
+                if w2g is None:
+                    w2g = K.scale_rows_bf16(blk.mlp.fc2.weight.detach(), blk.gamma.detach())
+                K.linear_dgrad(dsrc, w2g, out=dh, epilogue=nv.SV_EPI_MUL_AUX, aux=gh, compute_bf16=True, policy=pol)
             # fc1 data gradient with the LayerNorm backward in its epilogue (C = 512 / 1024: dy never reaches HBM);
             # None where the fused form does not apply -> the two passes
             fused = K.linear_dgrad_ln(dh, w1, z.view(M, C), mean, rstd, blk.norm.weight, dw=g(blk.norm.weight),
@@ -647,17 +729,25 @@ class ConvNeXtHip(nn.Module):
             return folds
 
         with torch.cuda.stream(side):
-            K.layerscale_wgrad(dsrc, a, blk.mlp.fc2.weight.detach(), blk.gamma.detach(), blk.mlp.fc2.bias.detach(),
-                               dw2=g(blk.mlp.fc2.weight), dgamma=g(blk.gamma), db2=g(blk.mlp.fc2.bias),
-                               compute_bf16=True, policy=spol, wgrad_target=self.wgrad_target)
+            if self.use_grn:
+                # V2: dW2 = d^T u, db2 = colsum(d); the GRN weight / bias gradients were added on the main stream
+                # before the hand-off, so this stream's _ready covers them
+                K.linear_wgrad(dsrc, grn_saved[0], out=g(blk.mlp.fc2.weight), accumulate=True,
+                               bias_out=g(blk.mlp.fc2.bias), compute_bf16=True, policy=spol,
+                               wgrad_target=self.wgrad_target)
+            else:
+                K.layerscale_wgrad(dsrc, a, blk.mlp.fc2.weight.detach(), blk.gamma.detach(),
+                                   blk.mlp.fc2.bias.detach(), dw2=g(blk.mlp.fc2.weight), dgamma=g(blk.gamma),
+                                   db2=g(blk.mlp.fc2.bias), compute_bf16=True, policy=spol,
+                                   wgrad_target=self.wgrad_target)
             if tail is None:
                 folds = rest(spol)
                 self._ready([blk.conv_dw.weight, blk.conv_dw.bias, blk.norm.weight, blk.norm.bias,
-                             blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.gamma])
+                             blk.mlp.fc1.weight, blk.mlp.fc1.bias, *self._fc2_params(blk)])
             else:
                 folds = None
-                self._ready([blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.gamma])
-            pending.append((side.record_event(), (dsrc, dh, dz, ln_finish, x, y, a, folds)))
+                self._ready(self._fc2_params(blk))
+            pending.append((side.record_event(), (dsrc, dh, dz, ln_finish, x, y, a, grn_saved, folds)))
         if tail is not None:
             def job(_rest=rest, _pol=pol):
                 _rest(_pol)
@@ -672,4 +762,4 @@ def create_convnext(name: str, precision: str = "bf16") -> ConvNeXtHip:
     if key not in CONVNEXT_CFGS:
         raise ValueError(f"unsupported ConvNeXt variant {name!r}")
     depths, dims = CONVNEXT_CFGS[key]
-    return ConvNeXtHip(depths, dims, precision=precision)
+    return ConvNeXtHip(depths, dims, precision=precision, use_grn=key.startswith("convnextv2"))

@@ -642,6 +642,121 @@ def layernorm_bwd(dy2d, x2d, mean, rstd, w, *, dw, db, dx=None, accumulate_dx=Fa
 
 
 # ----------------------------------------------------------------------------------------------
+# Global Response Normalization (ConvNeXt V2, csrc/grn.hip)
+EPS_GRN = 1e-6
+
+
+def _grn_act(who: str, B: int, *ts) -> tuple[int, int]:
+    """Checks of the [B*HW, n] activations of one GRN launch (same shape and dtype); returns (HW, n)."""
+    t0 = ts[0]
+    _check(t0.dim() == 2 and B > 0 and t0.shape[0] % B == 0 and t0.shape[0] > 0,
+           f"{who}: activations must be [B*HW, n] with B={B} dividing the rows")
+    _check(t0.shape[1] % 8 == 0, f"{who}: n={t0.shape[1]} must be a multiple of 8")
+    _check(t0.dtype in (torch.float32, torch.bfloat16), f"{who}: activations must be f32 or bf16")
+    for t in ts:
+        _check(t.is_cuda and t.shape == t0.shape and t.dtype == t0.dtype and t.is_contiguous()
+               and t.data_ptr() % 16 == 0,
+               f"{who}: activations must be contiguous, 16-byte aligned device tensors of one shape and dtype")
+    return t0.shape[0] // B, t0.shape[1]
+
+
+def _grn_f32(who: str, numel: int, *ts) -> None:
+    for t in ts:
+        _check(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel
+               and t.data_ptr() % 16 == 0, f"{who}: expected contiguous 16-byte aligned f32 tensors of {numel} elements")
+
+
+def grn_nparts(HW: int, n: int) -> int:
+    return value("sv_grn_nparts", HW, n)
+
+
+def grn_stats(a2d: torch.Tensor, B: int) -> torch.Tensor:
+    """Per-chunk sums of a^2: f32 partials [B, P, n], P = grn_nparts(HW, n)."""
+    HW, n = _grn_act("grn_stats", B, a2d)
+    part = torch.empty(B, grn_nparts(HW, n), n, device=a2d.device, dtype=torch.float32)
+    _timed_call("grn_stats", float(a2d.numel() * a2d.element_size()), "sv_grn_stats", ptr(a2d), dt(a2d),
+                ptr(part), B, HW, n)
+    return part
+
+
+def grn_finish(part: torch.Tensor, gamma: torch.Tensor, *, eps: float = EPS_GRN) -> tuple:
+    """Folds the partials of grn_stats; returns (G, N, scale = 1 + gamma N) as [B, n] and D as [B], all f32."""
+    _check(part.dim() == 3, "grn_finish: partials must be [B, P, n]")
+    B, P, n = part.shape
+    _grn_f32("grn_finish", B * P * n, part)
+    _grn_f32("grn_finish", n, gamma)
+    G, N, scale = (torch.empty(B, n, device=part.device, dtype=torch.float32) for _ in range(3))
+    D = torch.empty(B, device=part.device, dtype=torch.float32)
+    call("sv_grn_finish", ptr(part), P, ptr(gamma), ptr(G), ptr(N), ptr(scale), ptr(D), B, n, float(eps))
+    return G, N, scale, D
+
+
+def grn_apply(a2d: torch.Tensor, scale: torch.Tensor, beta: torch.Tensor, *, out: torch.Tensor | None = None):
+    """u = a * scale[b, c] + beta[c] in a's dtype; ``out`` may be ``a2d`` itself (the eval forward keeps no a)."""
+    B = scale.shape[0]
+    if out is None:
+        out = torch.empty_like(a2d)
+    HW, n = _grn_act("grn_apply", B, a2d, out)
+    _grn_f32("grn_apply", B * n, scale)
+    _grn_f32("grn_apply", n, beta)
+    _timed_call("grn_apply", 2.0 * a2d.numel() * a2d.element_size(), "sv_grn_apply", ptr(a2d), dt(a2d), ptr(scale),
+                ptr(beta), ptr(out), B, HW, n)
+    return out
+
+
+def grn_fwd(a2d: torch.Tensor, B: int, gamma: torch.Tensor, beta: torch.Tensor, *, inplace: bool = False) -> tuple:
+    """The three forward passes; returns (u, (G, N, scale, D))."""
+    st = grn_finish(grn_stats(a2d, B), gamma)
+    return grn_apply(a2d, st[2], beta, out=a2d if inplace else None), st
+
+
+def grn_bwd_stats(du2d: torch.Tensor, a2d: torch.Tensor, B: int) -> tuple:
+    """Per-chunk sums of du * a and of du: two f32 partial buffers [B, P, n]."""
+    HW, n = _grn_act("grn_bwd_stats", B, du2d, a2d)
+    P = grn_nparts(HW, n)
+    sp = torch.empty(B, P, n, device=a2d.device, dtype=torch.float32)
+    dp = torch.empty_like(sp)
+    _timed_call("grn_bwd_stats", 2.0 * a2d.numel() * a2d.element_size(), "sv_grn_bwd_stats",
+                ptr(du2d), ptr(a2d), dt(a2d), ptr(sp), ptr(dp), B, HW, n)
+    return sp, dp
+
+
+def grn_bwd_finish(sp: torch.Tensor, dp: torch.Tensor, gamma, G, N, D, *, dgamma, dbeta, accumulate: bool = True):
+    """Folds the partials of grn_bwd_stats (their chunk 0 then holds the per-image totals S and sum du); returns
+    k = dG / G [B, n] and writes / adds dgamma and dbeta."""
+    _check(sp.dim() == 3 and dp.shape == sp.shape, "grn_bwd_finish: partials must be two [B, P, n] buffers")
+    B, P, n = sp.shape
+    _grn_f32("grn_bwd_finish", B * P * n, sp, dp)
+    _grn_f32("grn_bwd_finish", B * n, G, N)
+    _grn_f32("grn_bwd_finish", n, gamma, dgamma, dbeta)
+    _check(D.is_cuda and D.dtype == torch.float32 and D.numel() == B and D.is_contiguous(), "grn_bwd_finish: bad D")
+    k = torch.empty(B, n, device=sp.device, dtype=torch.float32)
+    call("sv_grn_bwd_finish", ptr(sp), ptr(dp), P, ptr(gamma), ptr(G), ptr(N), ptr(D), ptr(k), ptr(dgamma),
+         ptr(dbeta), int(bool(accumulate)), B, n)
+    return k
+
+
+def grn_bwd_apply(du2d, a2d, gh2d, scale, k, *, out: torch.Tensor | None = None):
+    """dh = (du * scale[b, c] + a * k[b, c]) * gh in the activations' dtype; ``out`` may be ``du2d`` itself."""
+    B = scale.shape[0]
+    if out is None:
+        out = torch.empty_like(du2d)
+    HW, n = _grn_act("grn_bwd_apply", B, du2d, a2d, gh2d, out)
+    _grn_f32("grn_bwd_apply", B * n, scale, k)
+    _timed_call("grn_bwd_apply", 4.0 * a2d.numel() * a2d.element_size(), "sv_grn_bwd_apply", ptr(du2d), ptr(a2d),
+                ptr(gh2d), dt(a2d), ptr(scale), ptr(k), ptr(out), B, HW, n)
+    return out
+
+
+def grn_bwd(du2d, a2d, gh2d, B: int, gamma, stats: tuple, *, dgamma, dbeta):
+    """The three backward passes, in place over du: returns dh (= du2d's storage)."""
+    G, N, scale, D = stats
+    sp, dp = grn_bwd_stats(du2d, a2d, B)
+    k = grn_bwd_finish(sp, dp, gamma, G, N, D, dgamma=dgamma, dbeta=dbeta)
+    return grn_bwd_apply(du2d, a2d, gh2d, scale, k, out=du2d)
+
+
+# ----------------------------------------------------------------------------------------------
 # depthwise 7x7 + LN
 # The depthwise conv on the matrix cores (csrc/dwmfma.hip, round 6): per channel a banded-Toeplitz GEMM along the image
 # row on v_mfma_f32_16x16x32_bf16, with bf16 operands (the precision torch.autocast gives conv_dw).  Default: the bf16

@@ -126,6 +126,13 @@ _SIGS = {
     "sv_layernorm_fwd": [_p, _i32, _p, _p, _p, _i32, _p, _p, _i64, _i32, _f32, _p],
     "sv_layernorm_bwd_nparts": [_i64, _i32],
     "sv_layernorm_bwd": [_p, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _i64, _i32, _p],
+    "sv_grn_nparts": [_i64, _i32],
+    "sv_grn_stats": [_p, _i32, _p, _i32, _i64, _i32, _p],
+    "sv_grn_finish": [_p, _i32, _p, _p, _p, _p, _p, _i32, _i32, _f32, _p],
+    "sv_grn_apply": [_p, _i32, _p, _p, _p, _i32, _i64, _i32, _p],
+    "sv_grn_bwd_stats": [_p, _p, _i32, _p, _p, _i32, _i64, _i32, _p],
+    "sv_grn_bwd_finish": [_p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
+    "sv_grn_bwd_apply": [_p, _p, _p, _i32, _p, _p, _p, _i32, _i64, _i32, _p],
     "sv_dwconv7_ln_fwd": [_p, _i32, _p, _p, _p, _p, _f32, _p, _i32, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _p],
     "sv_dwconv7_bwd_data": [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_dwconv7_fwd_mfma": [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
