@@ -232,7 +232,7 @@ def floor_check(hip: dict, emu64: dict, emu32: dict, *, ratio_median: float, rat
 
 # ==============================================================================================================
 # ConvNeXt: the HIP bf16 path's store points, restated from spine-vision_amd/backbone/
-# convnext.py (``_forward_impl``, ``_block_backward_lean``, ``_backward_impl``) and the kernels it calls
+# convnext.py (``_forward_impl``, ``_block_backward``, ``_backward_impl``) and the kernels it calls
 # (spine-vision_amd/kernels.py), over the timm ConvNeXt of oracle/convnext.py (reference backbone.py:50,164-170):
 #
 #   forward   stem     P = bf16(image patches);  z0 = bf16(P . bf16(W)^T + b);  x = LN(z0) (f32, stats of bf16 z0)

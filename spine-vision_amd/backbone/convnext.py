@@ -11,7 +11,8 @@ spine_vision/training/models/backbone.py:166-170 (timm 1.0.22 ``timm/models/conv
   fc2 GEMM (+bias, *gamma, +residual)}, downsample LN+patch GEMM, pool+LN.  Backward writes the
   parameter gradients straight into ``p.grad`` (views of the trainer's flat gradient buffer) and
   calls ``grad_ready_hook`` after each block so the DDP bucketer can start its all-reduce while the
-  remaining blocks are still being differentiated.
+  remaining blocks are still being differentiated.  One ``_block_backward`` issues a block's kernels; where its
+  weight-gradient jobs run (inline, eager or lean) is ``_WgradSchedule``'s decision.
 * ``precision="bf16"``: bf16 MFMA, bf16 saved activations, f32 residual/gradient streams, f32
   master weights.  ``precision="fp32"``: every tensor f32 and f32 MFMA (parity mode, <=1e-3 vs the
   reference CPU path).
@@ -28,7 +29,6 @@ spine_vision/training/models/backbone.py:166-170 (timm 1.0.22 ``timm/models/conv
 from __future__ import annotations
 
 import os
-from contextlib import nullcontext as _nullctx
 from dataclasses import dataclass, field
 from typing import Callable
 
@@ -37,6 +37,7 @@ import torch.nn as nn
 
 from .. import kernels as K
 from .. import native as nv
+from ._explicit import ExplicitBackward
 
 CONVNEXT_CFGS = {
     "convnext_tiny": ((3, 3, 9, 3), (96, 192, 384, 768)),
@@ -155,7 +156,72 @@ class _ConvNeXtFn(torch.autograd.Function):
 _TAIL_MAIN = int(os.environ.get("SV_TAIL_MAIN", "0"))
 
 
-class ConvNeXtHip(nn.Module):
+class _WgradSchedule:
+    """Where a block's weight-gradient jobs run (DESIGN.md "ConvNeXt step").  A job is a callable taking the GEMM
+    policy of the stream it runs on: ``pol`` on the main stream, the side policy (``side_impl``, the grid under
+    ``side_grid_cap``, raised wave priority ``side_prio``) on the side stream.  ``ready``: the parameters to report
+    once the job has been issued, on its stream.
+
+    * inline (no side stream): a job runs on the main stream where it is submitted.
+    * eager (side stream, not lean): a job runs on the side stream where it is submitted, behind a main->side
+      hand-off of its own, its operands kept alive by ``record_stream``.
+    * lean (bf16, side stream, ``lean_sync``): jobs queue up until ``flush`` runs them on the side stream behind the
+      block's ONE hand-off; the queued closures hold their operands, kept in ``pending`` until the side stream has
+      passed them (``_release_side``) -- every cross-stream event / allocator event is a release packet (L2
+      write-back).  The side stream's GEMMs run at raised wave priority where they share a CU with the main stream's
+      data-gradient GEMMs (+1.0 % step, interleaved A/B; raising the main stream's instead cost 0.7 %)."""
+
+    def __init__(self, model, main, side, lean: bool, pol) -> None:
+        self.model, self.main, self.side, self.lean, self.pol = model, main, side, lean, pol
+        cap = pol.grid_cap
+        if model.side_grid_cap is not None:
+            cap = min(model.side_grid_cap, cap) if cap > 0 else model.side_grid_cap
+        self.spol = nv.policy(impl=model.side_impl, grid_cap=cap, wg_per_cu=pol.wg_per_cu, priority=model.side_prio)
+        self.queue: list = []  # lean: the current block's (job, ready)
+        # lean: per block (side-stream event, the jobs whose operands the side stream reads), oldest first
+        self.pending: list = []
+        self.tail: list = []  # the last block's jobs the main stream runs itself (_TAIL_MAIN)
+
+    def _run(self, jobs, pol) -> None:
+        for job, ready in jobs:
+            job(pol)
+            if ready:
+                self.model._ready(ready)
+
+    def submit(self, job, operands, ready=None) -> None:
+        if self.lean:
+            self.queue.append((job, ready))
+        elif self.side is None:
+            self._run([(job, ready)], self.pol)
+        else:
+            self.side.wait_event(self.main.record_event())
+            for t_ in operands:
+                t_.record_stream(self.side)
+            with torch.cuda.stream(self.side):
+                self._run([(job, ready)], self.spol)
+
+    def handoff(self) -> None:
+        if self.lean:
+            nv.handoff(self.main, self.side)
+
+    def flush(self, tail: bool) -> None:
+        """lean: the queued jobs on the side stream; with ``tail`` only the first (the fc2 weight gradient), the
+        rest wait for ``run_tail``."""
+        if not self.lean:
+            return
+        queue, self.queue = self.queue, []
+        n = 1 if tail else len(queue)
+        with torch.cuda.stream(self.side):
+            self._run(queue[:n], self.spol)
+            self.pending.append((self.side.record_event(), queue))
+        self.tail += queue[n:]
+
+    def run_tail(self) -> None:
+        self._run(self.tail, self.pol)
+        self.tail.clear()
+
+
+class ConvNeXtHip(ExplicitBackward, nn.Module):
     def __init__(self, depths=(3, 3, 27, 3), dims=(128, 256, 512, 1024), ls_init_value: float = 1e-6,
                  precision: str = "bf16", use_grn: bool = False) -> None:
         super().__init__()
@@ -435,34 +501,17 @@ class ConvNeXtHip(nn.Module):
         return (self.fused_mlp_bwd and not self.use_grn and self.compute_bf16 and self.overlap_wgrad and self.lean_sync
                 and blk.conv_dw.weight.shape[0] in K.MLP_BWD_FUSED_C)
 
-    def _side_stream(self, device) -> torch.cuda.Stream:
-        """The weight-gradient side stream; CU-masked (never on the CUs reserved for RCCL, training/cumask.py) when
-        StepEngine asks for it (comm_reserve_cus > 0 and SV_COMM_CU_MASK=1)."""
-        key = (device, self.comm_reserve_cus, self.comm_cu_mask)
-        if key not in self._side:
-            if self.comm_reserve_cus > 0 and self.comm_cu_mask:
-                from ..training.cumask import reserved_stream
-
-                self._side[key] = reserved_stream(device, self.comm_reserve_cus, "side")
-            else:
-                self._side[key] = torch.cuda.Stream(device=device)
-        return self._side[key]
-
-    @staticmethod
-    def _grad(p: torch.Tensor) -> torch.Tensor:
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
-    def _ready(self, params: list) -> None:
-        if self.grad_ready_hook is not None:
-            self.grad_ready_hook(params)
-
     def _fc2_params(self, blk) -> list:
         """The parameters whose gradients the fc2 stage of a block's backward writes."""
         if self.use_grn:
             return [blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.mlp.grn.weight, blk.mlp.grn.bias]
         return [blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.gamma]
+
+    @staticmethod
+    def _rest_params(blk) -> list:
+        """... and the block's other parameters: the fc1, LayerNorm and depthwise stages'."""
+        return [blk.conv_dw.weight, blk.conv_dw.bias, blk.norm.weight, blk.norm.bias, blk.mlp.fc1.weight,
+                blk.mlp.fc1.bias]
 
     def _grn_dgrad(self, blk, dsrc, a, gh, grn_saved, dh, cache, pol) -> None:
         """V2 fc2 stage of the data-gradient chain: du = d W2 (plain store) into ``dh``, then the GRN backward
@@ -475,10 +524,117 @@ class ConvNeXtHip(nn.Module):
         K.grn_bwd(dh, a, gh, gst[0].shape[0], grn.weight, gst, dgamma=self._grad(grn.weight),
                   dbeta=self._grad(grn.bias))
 
+    def _block_backward(self, blk, saved, d, db, cache, tape, sched: _WgradSchedule, tail: bool = False):
+        """Backward of one block given the gradient stream ``d`` (f32) and its bf16 copy ``db`` (bf16 mode); returns
+        the new (d, db).  The data-gradient chain runs on the main stream: fc2 dgrad (x GELU'), fc1 dgrad, LayerNorm
+        backward, depthwise backward-data.  The weight gradients (wgrad GEMMs, split-K folds, depthwise wgrad:
+        MFMA-bound with small outputs, where the dgrads are epilogue / HBM-bound, so the two overlap on the chip) are
+        three jobs handed to ``sched``, which decides where and when they run.  Every schedule issues the same
+        kernels with the same split-K depths (``wgrad_target``), so every schedule gives the same bits, at every
+        shape.
+
+        ``tail`` (lean, the backward's last block): the side stream, about one block behind the main stream, would
+        run this block's three jobs after the main stream has finished (the step's end waited ~0.5 ms on it, r11k
+        trace); only the fc2 one goes there, the other two run on the main stream (``sched.run_tail``)."""
+        bf, act, g = self.compute_bf16, self.act_dtype, self._grad
+        main, side, pol = sched.main, sched.side, sched.pol
+        x, z, y, mean, rstd, gh, a, grn_saved = saved
+        B, H, W, C = x.shape
+        M = B * H * W
+        fc1, fc2 = blk.mlp.fc1, blk.mlp.fc2
+        dsrc = db.view(M, C) if bf else d.view(M, C)
+        u = grn_saved[0] if self.use_grn else a  # the operand fc2 read: V2's GRN output
+        fc2_ps, rest_ps = self._fc2_params(blk), self._rest_params(blk)
+        folds: list | None = [] if self.merge_folds else None  # ONE fold launch for jobs (b) and (c), not four
+
+        def fc2_wgrad(policy):  # job (a)
+            if self.use_grn:
+                # V2 (no layer scale): dW2 = d^T u, db2 = colsum(d); the GRN weight / bias gradients are added on
+                # the main stream (_grn_dgrad), before the hand-off that the stream reporting them waits behind
+                K.linear_wgrad(dsrc, u, out=g(fc2.weight), accumulate=True, bias_out=g(fc2.bias), compute_bf16=bf,
+                               policy=policy, wgrad_target=self.wgrad_target)
+            else:
+                # dW2 = gamma (.) d^T a, dgamma = rowdot(W2, d^T a) + b2 (.) colsum(d), db2 = gamma (.) colsum(d)
+                K.layerscale_wgrad(dsrc, a, fc2.weight.detach(), blk.gamma.detach(), fc2.bias.detach(),
+                                   dw2=g(fc2.weight), dgamma=g(blk.gamma), db2=g(fc2.bias), compute_bf16=bf,
+                                   policy=policy, wgrad_target=self.wgrad_target)
+
+        def fc1_wgrad(policy):  # job (b): dW1 = dh^T y, db1 = colsum(dh) (fused in the wgrad GEMM)
+            K.linear_wgrad(dh, y, out=g(fc1.weight), accumulate=True, bias_out=g(fc1.bias), compute_bf16=bf,
+                           defer=folds, policy=policy, wgrad_target=self.wgrad_target)
+
+        def rest_wgrad(policy):  # job (c): the LayerNorm weight / bias fold, the depthwise wgrad, the block's folds
+            ln_finish(record=not sched.lean, defer=folds)  # (lean: the partials stay referenced in sched.pending)
+            K.dwconv7_bwd_weight(dz4, x, dw=g(blk.conv_dw.weight), db=g(blk.conv_dw.bias), defer=folds)
+            if folds is not None:
+                K.reduce_multi(folds)
+
+        sched.submit(fc2_wgrad, (dsrc, u), ready=fc2_ps if tail else None)
+        # fp32: the fc2 wgrad reads d itself, which the depthwise backward-data below updates in place
+        ev_w2 = side.record_event() if side is not None and not bf else None
+        # fc2: dh = ((d * gamma) @ W2) * GELU'(h), GELU'(h) stored by the forward epilogue; fc1: dy = dh @ W1; then
+        # the LayerNorm backward.  bf16 mode: dh, dy and dz travel as bf16 (the depthwise backward reads dz through
+        # its LDS-DMA ring, where 2-byte columns cost no more than 4-byte ones)
+        dh = torch.empty(M, 4 * C, device=d.device, dtype=act)
+        wt = tape.wt.pop(id(blk), None)
+        if wt is not None:
+            # fused (lean only): fc2 data gradient (x GELU') -> fc1 data gradient -> LayerNorm backward in one kernel
+            dz = torch.empty(M, C, device=d.device, dtype=torch.bfloat16)
+            part, P = K.mlp_bwd(dsrc, wt[0], gh, wt[1], z.view(M, C), mean, rstd, blk.norm.weight, dh=dh, dz=dz)
+            dw_ln, db_ln = g(blk.norm.weight), g(blk.norm.bias)
+
+            def ln_finish(record: bool = True, defer: list | None = None):
+                if defer is not None:
+                    defer += [(part[0], dw_ln, P, True), (part[1], db_ln, P, True)]
+                else:
+                    K.reduce_pair(part[0], dw_ln, part[1], db_ln, P)
+        elif self.use_grn:
+            self._grn_dgrad(blk, dsrc, a, gh, grn_saved, dh, cache, pol)
+        elif bf:
+            # gamma folded into a bf16 copy of W2, made beside the forward where the side stream is on
+            w2g = tape.w2g.pop(id(blk), None)
+            if w2g is None:
+                w2g = K.scale_rows_bf16(fc2.weight.detach(), blk.gamma.detach())
+            K.linear_dgrad(dsrc, w2g, out=dh, epilogue=nv.SV_EPI_MUL_AUX, aux=gh, compute_bf16=True, policy=pol)
+        else:
+            K.linear_dgrad(dsrc, fc2.weight.detach(), out=dh, epilogue=nv.SV_EPI_MUL_AUX, a_scale_k=blk.gamma, aux=gh,
+                           compute_bf16=False, policy=pol)
+        sched.submit(fc1_wgrad, (dh, y))
+        if wt is None:
+            w1 = self._w(fc1.weight, cache)
+            # bf16: the LayerNorm backward in the fc1 data gradient's epilogue (C = 512 / 1024: dy never reaches
+            # HBM); None where that form does not apply -> the two passes, the LayerNorm weight / bias partials
+            # folded by job (c), off the data-gradient chain
+            fused = K.linear_dgrad_ln(dh, w1, z.view(M, C), mean, rstd, blk.norm.weight, dw=g(blk.norm.weight),
+                                      db=g(blk.norm.bias), policy=pol) if bf else None
+            if fused is not None:
+                dz, ln_finish = fused
+            else:
+                dy = torch.empty(M, C, device=d.device, dtype=act)
+                K.linear_dgrad(dh, w1, out=dy, compute_bf16=bf, policy=pol)
+                dz, ln_finish = K.layernorm_bwd(dy, z.view(M, C), mean, rstd, blk.norm.weight, dw=g(blk.norm.weight),
+                                                db=g(blk.norm.bias), out_dtype=act, defer_reduce=True)
+        dz4 = dz.view(B, H, W, C)
+        # every gradient of the block is final on the reporting stream after job (c): the bucketer's event covers
+        # them all
+        sched.submit(rest_wgrad, (dz, x), ready=rest_ps if tail else rest_ps + fc2_ps)
+        # lean: the main stream's next launch is enqueued before the side stream's jobs: the depthwise backward-data
+        # needs only dz, and the host's side-stream enqueues left the main queue idle ~18 us per block before it the
+        # other way round (r13n trace, queue_gaps.py)
+        sched.handoff()
+        if side is not None and bf:
+            # d += dwconv^T(dz) in place; its bf16 copy goes to a fresh buffer: the side stream's fc2 wgrad may still
+            # be reading the previous one (kept alive by the schedule), so the main stream does not wait for it
+            db = torch.empty_like(db)
+        elif side is not None:
+            main.wait_event(ev_w2)
+        K.dwconv7_bwd_data(dz4, blk.conv_dw.weight, d, accumulate=True, dx_bf16=db)
+        sched.flush(tail)
+        return d, db
+
     @torch.no_grad()
     def _backward_impl(self, tape: _Tape, dfeat: torch.Tensor) -> None:
         bf = self.compute_bf16
-        act = self.act_dtype
         cache: dict = tape.wcache
         g = self._grad
         hn = self.head.norm
@@ -491,11 +647,7 @@ class ConvNeXtHip(nn.Module):
         if self.main_bwd_cap > 0:
             comm_cap = min(comm_cap, self.main_bwd_cap) if comm_cap > 0 else self.main_bwd_cap
         pol = nv.policy(grid_cap=comm_cap, wg_per_cu=self.side_wg_per_cu if side is not None else 0)
-        lean = side is not None and bf and self.lean_sync
-        tail: list = []  # the last block's weight gradients the main stream runs after the stem (_TAIL_MAIN)
-        # lean mode: per block (side-stream event, the operands the side stream reads), oldest first;
-        # released in batches once the side stream has passed them (_release_side)
-        pending: list = []
+        sched = _WgradSchedule(self, main, side, side is not None and bf and self.lean_sync, pol)
         # d: f32 gradient stream (residual accumulation); db: its bf16 copy, the GEMM operand (bf16 mode)
         d, db = K.pool_ln_bwd(dfeat.float(), *tape.pool, hn.weight, tape.out_shape, dlnw=g(hn.weight),
                               dlnb=g(hn.bias), with_bf16=bf)
@@ -506,103 +658,14 @@ class ConvNeXtHip(nn.Module):
             for bi in range(len(blocks_saved) - 1, -1, -1):
                 blk, saved = st.blocks[bi], blocks_saved[bi]
                 # the tape lets go of the block: its main-stream reads are stream-ordered before any
-                # later main-stream allocation, its side-stream reads stay referenced below
+                # later main-stream allocation, its side-stream reads stay referenced by the schedule
                 blocks_saved[bi] = None
-                x, z, y, mean, rstd, gh, a, grn_saved = saved
-                B, H, W, C = x.shape
-                M = B * H * W
-                d2 = d.view(M, C)
-                w1 = self._w(blk.mlp.fc1.weight, cache)
-                dsrc = db.view(M, C) if bf else d2
-                if lean:
-                    last = st is self.stages[0] and bi == 0
-                    d, db = self._block_backward_lean(blk, saved, d, db, dsrc, cache, tape, main, side, pending, pol,
-                                                      tail=tail if last and _TAIL_MAIN else None)
-                    self._release_side(main, pending)
-                    if last and _TAIL_MAIN == 2:
-                        for job in tail:
-                            job()
-                        tail.clear()
-                    continue
-                # weight gradients (wgrad GEMMs, split-K reductions, depthwise wgrad) run on the side
-                # stream beside the data-gradient chain of the main stream: the wgrads are MFMA-bound
-                # with small outputs, the dgrads epilogue/HBM-bound, so the two overlap on the chip
-                if side is not None:
-                    side.wait_event(main.record_event())
-                    for t_ in (dsrc, grn_saved[0] if self.use_grn else a):
-                        t_.record_stream(side)
-                with torch.cuda.stream(side) if side is not None else _nullctx():
-                    if self.use_grn:
-                        # V2 (no layer scale): dW2 = d^T u, db2 = colsum(d), u the GRN output fc2 read
-                        K.linear_wgrad(dsrc, grn_saved[0], out=g(blk.mlp.fc2.weight), accumulate=True,
-                                       bias_out=g(blk.mlp.fc2.bias), compute_bf16=bf, policy=pol)
-                    else:
-                        # dW2 = gamma (.) d^T a, dgamma = rowdot(W2, d^T a) + b2 (.) colsum(d), db2 = gamma (.) colsum(d)
-                        K.layerscale_wgrad(dsrc, a, blk.mlp.fc2.weight.detach(), blk.gamma.detach(),
-                                           blk.mlp.fc2.bias.detach(), dw2=g(blk.mlp.fc2.weight), dgamma=g(blk.gamma),
-                                           db2=g(blk.mlp.fc2.bias), compute_bf16=bf, policy=pol)
-                ev_w2 = side.record_event() if side is not None else None
-                # fc2: dh = ((d * gamma) @ W2) * GELU'(h).  bf16 mode folds gamma into a bf16 copy of W2;
-                # GELU'(h) was stored by the forward epilogue
-                dh = torch.empty(M, 4 * C, device=d.device, dtype=act)
-                if self.use_grn:
-                    self._grn_dgrad(blk, dsrc, a, gh, grn_saved, dh, cache, pol)
-                elif bf:
-                    w2g = tape.w2g.pop(id(blk), None)
-                    if w2g is None:
-                        w2g = K.scale_rows_bf16(blk.mlp.fc2.weight.detach(), blk.gamma.detach())
-                    K.linear_dgrad(dsrc, w2g, out=dh, epilogue=nv.SV_EPI_MUL_AUX, aux=gh, compute_bf16=True, policy=pol)
-                else:
-                    K.linear_dgrad(d2, blk.mlp.fc2.weight.detach(), out=dh, epilogue=nv.SV_EPI_MUL_AUX,
-                                   a_scale_k=blk.gamma, aux=gh, compute_bf16=False, policy=pol)
-                # fc1: dy = dh @ W1 (main) ; dW1 = dh^T y, db1 = colsum(dh) (side, fused in the wgrad GEMM).
-                # bf16 mode: dy and dz travel as bf16 (the depthwise backward reads dz through its LDS-DMA
-                # ring, where 2-byte columns cost no more than 4-byte ones)
-                if side is not None:
-                    side.wait_event(main.record_event())
-                    for t_ in (dh, y):
-                        t_.record_stream(side)
-                folds: list | None = [] if self.merge_folds else None  # one fold launch for the block
-                with torch.cuda.stream(side) if side is not None else _nullctx():
-                    K.linear_wgrad(dh, y, out=g(blk.mlp.fc1.weight), accumulate=True,
-                                   bias_out=g(blk.mlp.fc1.bias), compute_bf16=bf, defer=folds, policy=pol)
-                # bf16: the LayerNorm backward in the fc1 data gradient's epilogue where it applies (as the lean
-                # schedule does, so both schedules give the same bits)
-                fused = K.linear_dgrad_ln(dh, w1, z.view(M, C), mean, rstd, blk.norm.weight, dw=g(blk.norm.weight),
-                                          db=g(blk.norm.bias), policy=pol) if bf else None
-                if fused is not None:
-                    dz, ln_finish = fused
-                else:
-                    dy = torch.empty(M, C, device=d.device, dtype=act)
-                    K.linear_dgrad(dh, w1, out=dy, compute_bf16=bf, policy=pol)
-                    # LayerNorm + depthwise conv; d += dwconv^T(dz) in place, bf16 copy refreshed (old copy dead)
-                    # the LN weight/bias partials are folded on the side stream (off the data-gradient chain)
-                    dz, ln_finish = K.layernorm_bwd(dy, z.view(M, C), mean, rstd, blk.norm.weight,
-                                                    dw=g(blk.norm.weight), db=g(blk.norm.bias), out_dtype=act,
-                                                    defer_reduce=True)
-                dz4 = dz.view(B, H, W, C)
-                blk_params = [blk.conv_dw.weight, blk.conv_dw.bias, blk.norm.weight, blk.norm.bias,
-                              blk.mlp.fc1.weight, blk.mlp.fc1.bias, *self._fc2_params(blk)]
-                if side is not None:
-                    side.wait_event(main.record_event())
-                    for t_ in (dz, x):
-                        t_.record_stream(side)
-                with torch.cuda.stream(side) if side is not None else _nullctx():
-                    ln_finish(defer=folds)
-                    K.dwconv7_bwd_weight(dz4, x, dw=g(blk.conv_dw.weight), db=g(blk.conv_dw.bias), defer=folds)
-                    if folds is not None:
-                        K.reduce_multi(folds)
-                    # every gradient of the block is final on this stream now: the bucketer's event
-                    # covers them all
-                    self._ready(blk_params)
-                if side is not None and bf:
-                    # the bf16 copy of the gradient stream goes to a fresh buffer: the side stream's fc2
-                    # wgrad may still be reading the previous one (record_stream above keeps it alive), so
-                    # the main stream does not wait for the side stream here
-                    db = torch.empty_like(db)
-                elif side is not None:
-                    main.wait_event(ev_w2)  # fp32: the fc2 wgrad reads d itself, which is updated in place
-                K.dwconv7_bwd_data(dz4, blk.conv_dw.weight, d, accumulate=True, dx_bf16=db)
+                # the backward's last block (lean): its fc1 and depthwise weight gradients on the main stream
+                tail = sched.lean and _TAIL_MAIN > 0 and st is self.stages[0] and bi == 0
+                d, db = self._block_backward(blk, saved, d, db, cache, tape, sched, tail=tail)
+                self._release_side(main, sched.pending)
+                if _TAIL_MAIN == 2:
+                    sched.run_tail()
             if ds_saved is not None:
                 x_prev, patches, d_mean, d_rstd = ds_saved
                 ln, conv = st.downsample[0], st.downsample[1]
@@ -632,13 +695,11 @@ class ConvNeXtHip(nn.Module):
             s_mean, s_rstd = tape.stem
             K.stem_bwd(tape.img, conv.weight, conv.bias, ln.weight, s_mean, s_rstd, d, dw=g(conv.weight),
                        db=g(conv.bias), dlnw=g(ln.weight), dlnb=g(ln.bias))
-        for job in tail:
-            job()
+        sched.run_tail()
         if side is not None:
             main.wait_stream(side)  # clip / AdamW / the next step see every side-stream gradient
-            pending.clear()  # safe: later main-stream allocations are ordered after the join
+            sched.pending.clear()  # safe: later main-stream allocations are ordered after the join
         self._ready([conv.weight, conv.bias, ln.weight, ln.bias])
-
 
     # lean mode keeps at most 2 x _RELEASE_BATCH blocks of side-stream operands (dh alone is M x 4C
     # bf16) instead of every block's until the backward ends; one main->side wait per batch
@@ -654,107 +715,6 @@ class ConvNeXtHip(nn.Module):
         if len(pending) >= 2 * cls._RELEASE_BATCH:
             main.wait_event(pending[cls._RELEASE_BATCH - 1][0])
             del pending[:cls._RELEASE_BATCH]
-
-    def _block_backward_lean(self, blk, saved, d, db, dsrc, cache, tape, main, side, pending, pol, tail=None):
-        """bf16 block backward with one main->side hand-off.  Main: fc2 dgrad (x GELU'), fc1 dgrad,
-        LayerNorm backward, depthwise backward-data.  Side, after the LayerNorm backward: fc2 wgrad
-        (+ gamma, bias), fc1 wgrad (+ bias), the LayerNorm weight/bias fold and the depthwise wgrad of
-        the block, beside the main stream's next block.  ``pol``: the main stream's GEMM policy; the side
-        stream's GEMMs run at raised wave priority where they share a CU with the main stream's data-gradient
-        GEMMs (+1.0% step, interleaved A/B gpurun_out prio2; raising the main stream's instead cost 0.7%,
-        prio1), under side_grid_cap when set.  Returns the new (d, db).
-
-        ``tail`` (the backward's last block): the side stream, about one block behind the main stream, would run
-        this block's three weight gradients after the main stream has finished (the step's end waited ~0.5 ms on
-        it, r11k trace); only the fc2 one goes there, and the fc1 and depthwise ones (with the block's fold) are
-        appended to ``tail`` for the main stream to run after the stem."""
-        g = self._grad
-        x, z, y, mean, rstd, gh, a, grn_saved = saved
-        B, H, W, C = x.shape
-        M = B * H * W
-        wt = tape.wt.pop(id(blk), None)
-        dh = torch.empty(M, 4 * C, device=d.device, dtype=torch.bfloat16)
-        if wt is not None:
-            # fused: fc2 data gradient (x GELU') -> fc1 data gradient -> LayerNorm backward in one kernel
-            dz = torch.empty(M, C, device=d.device, dtype=torch.bfloat16)
-            part, P = K.mlp_bwd(dsrc, wt[0], gh, wt[1], z.view(M, C), mean, rstd, blk.norm.weight, dh=dh, dz=dz)
-            dw_ln, db_ln = g(blk.norm.weight), g(blk.norm.bias)
-
-            def ln_finish(record: bool = True, defer: list | None = None, _p=part, _n=P):
-                if defer is not None:
-                    defer += [(_p[0], dw_ln, _n, True), (_p[1], db_ln, _n, True)]
-                else:
-                    K.reduce_pair(_p[0], dw_ln, _p[1], db_ln, _n)
-        else:
-            w1 = self._w(blk.mlp.fc1.weight, cache)
-            if self.use_grn:
-                self._grn_dgrad(blk, dsrc, a, gh, grn_saved, dh, cache, pol)
-            else:
-                w2g = tape.w2g.pop(id(blk), None)
-                if w2g is None:
-                    w2g = K.scale_rows_bf16(blk.mlp.fc2.weight.detach(), blk.gamma.detach())
-                K.linear_dgrad(dsrc, w2g, out=dh, epilogue=nv.SV_EPI_MUL_AUX, aux=gh, compute_bf16=True, policy=pol)
-            # fc1 data gradient with the LayerNorm backward in its epilogue (C = 512 / 1024: dy never reaches HBM);
-            # None where the fused form does not apply -> the two passes
-            fused = K.linear_dgrad_ln(dh, w1, z.view(M, C), mean, rstd, blk.norm.weight, dw=g(blk.norm.weight),
-                                      db=g(blk.norm.bias), policy=pol)
-            if fused is not None:
-                dz, ln_finish = fused
-            else:
-                dy = torch.empty(M, C, device=d.device, dtype=torch.bfloat16)
-                K.linear_dgrad(dh, w1, out=dy, compute_bf16=True, policy=pol)
-                dz, ln_finish = K.layernorm_bwd(dy, z.view(M, C), mean, rstd, blk.norm.weight, dw=g(blk.norm.weight),
-                                                db=g(blk.norm.bias), out_dtype=torch.bfloat16, defer_reduce=True)
-        dz4 = dz.view(B, H, W, C)
-        nv.handoff(main, side)
-        # the main stream's next launch is enqueued first: the depthwise backward-data needs only dz, and the host's
-        # side-stream enqueues below left the main queue idle ~18 us per block before it (r13n trace, queue_gaps.py).
-        # The side stream still reads dsrc (this block's bf16 gradient copy): the next copy gets a fresh buffer
-        db = torch.empty_like(db)
-        K.dwconv7_bwd_data(dz4, blk.conv_dw.weight, d, accumulate=True, dx_bf16=db)
-        side_cap = pol.grid_cap
-        if self.side_grid_cap is not None:
-            side_cap = min(self.side_grid_cap, side_cap) if side_cap > 0 else self.side_grid_cap
-        spol = nv.policy(impl=self.side_impl, grid_cap=side_cap, wg_per_cu=pol.wg_per_cu, priority=self.side_prio)
-        def rest(policy):
-            # the block's remaining folds (fc1 wgrad slab + bias, LayerNorm and depthwise weight / bias
-            # partials) in ONE launch instead of four
-            folds: list | None = [] if self.merge_folds else None
-            K.linear_wgrad(dh, y, out=g(blk.mlp.fc1.weight), accumulate=True, bias_out=g(blk.mlp.fc1.bias),
-                           compute_bf16=True, defer=folds, policy=policy, wgrad_target=self.wgrad_target)
-            ln_finish(record=False, defer=folds)
-            K.dwconv7_bwd_weight(dz4, x, dw=g(blk.conv_dw.weight), db=g(blk.conv_dw.bias), defer=folds)
-            if folds is not None:
-                K.reduce_multi(folds)
-            return folds
-
-        with torch.cuda.stream(side):
-            if self.use_grn:
-                # V2: dW2 = d^T u, db2 = colsum(d); the GRN weight / bias gradients were added on the main stream
-                # before the hand-off, so this stream's _ready covers them
-                K.linear_wgrad(dsrc, grn_saved[0], out=g(blk.mlp.fc2.weight), accumulate=True,
-                               bias_out=g(blk.mlp.fc2.bias), compute_bf16=True, policy=spol,
-                               wgrad_target=self.wgrad_target)
-            else:
-                K.layerscale_wgrad(dsrc, a, blk.mlp.fc2.weight.detach(), blk.gamma.detach(),
-                                   blk.mlp.fc2.bias.detach(), dw2=g(blk.mlp.fc2.weight), dgamma=g(blk.gamma),
-                                   db2=g(blk.mlp.fc2.bias), compute_bf16=True, policy=spol,
-                                   wgrad_target=self.wgrad_target)
-            if tail is None:
-                folds = rest(spol)
-                self._ready([blk.conv_dw.weight, blk.conv_dw.bias, blk.norm.weight, blk.norm.bias,
-                             blk.mlp.fc1.weight, blk.mlp.fc1.bias, *self._fc2_params(blk)])
-            else:
-                folds = None
-                self._ready(self._fc2_params(blk))
-            pending.append((side.record_event(), (dsrc, dh, dz, ln_finish, x, y, a, grn_saved, folds)))
-        if tail is not None:
-            def job(_rest=rest, _pol=pol):
-                _rest(_pol)
-                self._ready([blk.conv_dw.weight, blk.conv_dw.bias, blk.norm.weight, blk.norm.bias,
-                             blk.mlp.fc1.weight, blk.mlp.fc1.bias])
-            tail.append(job)
-        return d, db
 
 
 def create_convnext(name: str, precision: str = "bf16") -> ConvNeXtHip:

@@ -32,6 +32,7 @@ import torch.nn as nn
 
 from .. import kernels as K
 from .. import native as nv
+from ._explicit import ExplicitBackward
 
 # SV_MULTI_PACK=0: one weight-pack launch per conv in the forward (A/B runs)
 _MULTI_PACK = os.environ.get("SV_MULTI_PACK", "1") != "0"
@@ -129,7 +130,7 @@ class _Tape:
     batch_stats: bool = True  # train-mode BN (batch statistics) in the forward that made the tape
 
 
-class ResNetHip(nn.Module):
+class ResNetHip(ExplicitBackward, nn.Module):
     def __init__(self, kind: str = "bottleneck", layers=(3, 4, 6, 3), precision: str = "bf16") -> None:
         super().__init__()
         if precision not in ("bf16", "fp32"):
@@ -433,29 +434,6 @@ class ResNetHip(nn.Module):
         return feat, tape
 
     # -- backward ----------------------------------------------------------------------------------
-    @staticmethod
-    def _grad(p: torch.Tensor) -> torch.Tensor:
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
-    def _ready(self, params: list) -> None:
-        if self.grad_ready_hook is not None:
-            self.grad_ready_hook(params)
-
-    def _side_stream(self, device) -> torch.cuda.Stream:
-        """The weight-gradient side stream; CU-masked (never on the CUs reserved for RCCL, training/cumask.py) when
-        StepEngine asks for it (comm_reserve_cus > 0 and SV_COMM_CU_MASK=1)."""
-        key = (device, self.comm_reserve_cus, self.comm_cu_mask)
-        if key not in self._side:
-            if self.comm_reserve_cus > 0 and self.comm_cu_mask:
-                from ..training.cumask import reserved_stream
-
-                self._side[key] = reserved_stream(device, self.comm_reserve_cus, "side")
-            else:
-                self._side[key] = torch.cuda.Stream(device=device)
-        return self._side[key]
-
     def _flush_wgrads(self, jobs: list, params: list, side, keep: list, deferred: list | None = None,
                       pol: "nv.GemmPolicy | None" = None) -> None:
         """Run the block's weight gradients (conv_bwd_weight jobs) and report its parameters ready.  With a

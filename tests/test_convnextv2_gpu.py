@@ -98,18 +98,20 @@ def test_v2_bf16_no_farther_than_autocast(dev):
 
 
 def test_v2_bf16_schedules_bitwise_equal(dev):
-    """The plain backward (weight gradients on the main stream: SV_SIDE_STREAM=0, set through the model attribute) and
-    the lean side-stream backward run the same kernels: every gradient equal bit for bit."""
+    """The lean side-stream backward, the inline one (weight gradients on the main stream: SV_SIDE_STREAM=0, set
+    through the model attribute) and the eager side-stream one (SV_LEAN_SYNC=0) run the same kernels: every gradient
+    equal bit for bit."""
     _, img, _, _ = _reference("convnextv2_base")
     out = []
-    for overlap in (True, False):
+    for overlap, lean in ((True, True), (False, True), (True, False)):
         hip = _hip("convnextv2_base", "bf16", dev)
-        hip.overlap_wgrad = overlap
         assert hip.lean_sync
+        hip.overlap_wgrad, hip.lean_sync = overlap, lean
         out.append(_hip_grads(hip, img, dev))
-    assert torch.equal(out[0][0], out[1][0])
-    for n in out[0][1]:
-        assert torch.equal(out[0][1][n], out[1][1][n]), n
+    for f, grads in out[1:]:
+        assert torch.equal(out[0][0], f)
+        for n in out[0][1]:
+            assert torch.equal(out[0][1][n], grads[n]), n
 
 
 @pytest.mark.parametrize("precision,overlap", [("bf16", True), ("bf16", False), ("fp32", True)])

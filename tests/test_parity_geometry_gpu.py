@@ -176,7 +176,7 @@ def test_convnext_bf16_geometry(dev, name, res, B):
 
 
 @pytest.mark.parametrize("knob", ["lean_sync", "overlap_wgrad", "tail_main", "tail_main_before_stem"])
-def test_convnext_bf16_schedule_knobs_match_default(dev, knob, monkeypatch):
+def test_convnext_bf16_schedule_knobs_match_default(dev, knob, monkeypatch, B=2):
     """SV_LEAN_SYNC=0 / SV_SIDE_STREAM=0 / SV_TAIL_MAIN=0 change only WHERE the same kernels run (one main->side
     hand-off per block vs three; weight gradients on the side stream vs the main stream; the last block's fc1 and
     depthwise weight gradients after the stem on the main stream vs on the side stream): every gradient must equal
@@ -185,7 +185,7 @@ def test_convnext_bf16_schedule_knobs_match_default(dev, knob, monkeypatch):
     from spine_vision_amd.backbone import create_convnext
 
     ref = ow.fill_module(oc.create("convnext_base"))
-    img, _, _ = ow.localization_batch(2, 128, 128)
+    img, _, _ = ow.localization_batch(B, 128, 128)
     grads = []
     for off in (False, True):
         hip = create_convnext("convnext_base", precision="bf16")
@@ -203,6 +203,59 @@ def test_convnext_bf16_schedule_knobs_match_default(dev, knob, monkeypatch):
         grads.append([p.grad.detach().cpu().clone() for p in hip.parameters()])
     for a, b in zip(*grads):
         assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("knob", ["lean_sync", "overlap_wgrad"])
+def test_convnext_bf16_schedule_knobs_match_default_b8(dev, knob, monkeypatch):
+    """The same at B = 8, the smallest batch at which a weight gradient's split-K depth depends on its grid target
+    (S1 fc1, (M, N, K) = (8192, 512, 128): 64 slices at the library's default target of 128 workgroups, 128 at the
+    model's 256).  The slices are rounded to bf16 one by one, so the schedules agree bit for bit only if every one of
+    them passes the model's target."""
+    test_convnext_bf16_schedule_knobs_match_default(dev, knob, monkeypatch, B=8)
+
+
+def _v1_grads(dev, precision, seen=None, **knobs):
+    """One forward / backward of convnext_base at 2 x 64 x 64 on generated weights -> (the model, its gradients)."""
+    from spine_vision_amd.backbone import create_convnext
+
+    hip = create_convnext("convnext_base", precision=precision)
+    hip.load_state_dict(ow.fill_module(oc.create("convnext_base")).state_dict(), strict=True)
+    hip = hip.to(dev)
+    for k, v in knobs.items():
+        assert hasattr(hip, k)
+        setattr(hip, k, v)
+    if seen is not None:
+        hip.grad_ready_hook = seen.extend
+    img, _, _ = ow.localization_batch(2, 64, 64)
+    f = hip(img.to(dev))
+    f.backward(torch.from_numpy(ow.uniform("dfeat", f.numel(), -1, 1).reshape(f.shape)).to(dev))
+    torch.cuda.synchronize()
+    return hip, [p.grad.detach().cpu().clone() for p in hip.parameters()]
+
+
+def test_convnext_fp32_side_stream_matches_single_stream(dev):
+    """fp32 backward: the weight gradients on the side stream (a hand-off per job, the main stream waiting for the
+    fc2 weight gradient before it updates the gradient stream in place) against every kernel on the main stream:
+    same kernels, so every gradient must be equal bit for bit."""
+    grads = [_v1_grads(dev, "fp32", overlap_wgrad=overlap)[1] for overlap in (True, False)]
+    for a, b in zip(*grads):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("precision,knobs,tail_main", [
+    ("bf16", {}, 0), ("bf16", {"lean_sync": False}, 0), ("bf16", {"overlap_wgrad": False}, 0), ("fp32", {}, 0),
+    ("bf16", {}, 1), ("bf16", {}, 2)], ids=["lean", "eager", "inline", "fp32", "tail_main", "tail_main_before_stem"])
+def test_convnext_reports_every_parameter_ready(dev, precision, knobs, tail_main, monkeypatch):
+    """grad_ready_hook sees every trainable parameter exactly once in every schedule (a missing report leaves a DDP
+    bucket open)."""
+    from spine_vision_amd.backbone import convnext as cx
+
+    monkeypatch.setattr(cx, "_TAIL_MAIN", tail_main)
+    seen: list = []
+    hip, _ = _v1_grads(dev, precision, seen=seen, **knobs)
+    names = {id(p): n for n, p in hip.named_parameters()}
+    assert all(id(p) in names for p in seen)
+    assert sorted(names[id(p)] for p in seen) == sorted(n for n, p in hip.named_parameters() if p.requires_grad)
 
 
 def test_resnet_bf16_side_stream_matches_single_stream(dev):
