@@ -227,7 +227,8 @@ int sv_mlp_bwd(const uint16_t* d, const uint16_t* w2t, const uint16_t* gelu_grad
  * fwd: y = (x-mean)*rstd*w + b; saves mean/rstd [rows] (f32).
  * bwd: dx = rstd*(g - mean_c(g) - xhat*mean_c(g*xhat)), g = dy*w;  dx written (accumulate=0) or
  *      added (accumulate=1);  per-block partial sums of dw = sum dy*xhat, db = sum dy are written to
- *      dw_part/db_part [nparts][C]; nparts = sv_layernorm_bwd_nparts(rows, C).                       */
+ *      dw_part/db_part [nparts][C]; nparts = sv_layernorm_bwd_nparts(rows, C).
+ * C: 32, 96, 160 (4 lanes per row), 64 * {1, 2, 3, 4, 6, 8, 12, 16, 24} or 2048.                     */
 int sv_layernorm_fwd(const void* x, int32_t x_dtype, const float* w, const float* b, void* y,
                      int32_t y_dtype, float* mean, float* rstd, int64_t rows, int32_t C, float eps,
                      sv_stream_t stream);
@@ -269,7 +270,9 @@ int sv_grn_bwd_apply(const void* du, const void* a, const void* gh, int32_t dtyp
 /* ---- ConvNeXt block head: depthwise 7x7 (pad 3, bias) fused with the channels-last LayerNorm --
  * Replaces ConvNeXtBlock.conv_dw + permute + ConvNeXtBlock.norm (timm convnext.py).
  * x [B,H,W,C] (x_dtype), wdw [C][49] (timm weight [C,1,7,7]), bdw [C].
- * outputs: z = dwconv(x) (saved for backward, z_dtype), y = LN(z) (y_dtype), mean/rstd [B*H*W].  */
+ * outputs: z = dwconv(x) (saved for backward, z_dtype), y = LN(z) (y_dtype), mean/rstd [B*H*W].
+ * C % 32 == 0 here and in sv_dwconv7_bwd_data / _bwd_weight (C % 64 == 32: the last 64-channel group runs half
+ * masked, csrc/dwconv.hip), and C a width sv_layernorm_fwd takes.                                   */
 int sv_dwconv7_ln_fwd(const void* x, int32_t x_dtype, const float* wdw, const float* bdw,
                       const float* lnw, const float* lnb, float eps, void* z, int32_t z_dtype, void* y,
                       int32_t y_dtype, float* mean, float* rstd, int32_t B, int32_t H, int32_t W,
@@ -315,7 +318,8 @@ int sv_dwconv7_bwd_weight_mfma(const uint16_t* dz, const void* x, int32_t x_dtyp
 
 /* ---- ConvNeXt stem: Conv2d(3, C, k=4, s=4) + LayerNorm2d, fused --------------------------------
  * img: NCHW f32 [B,3,H,W] (ImageNet-normalised, = the reference batch["image"]); w [C][3*16]
- * (timm stem.0.weight), b [C]; y: NHWC [B,H/4,W/4,C] (y_dtype); mean/rstd [B*H/4*W/4].            */
+ * (timm stem.0.weight), b [C]; y: NHWC [B,H/4,W/4,C] (y_dtype); mean/rstd [B*H/4*W/4].
+ * C: 64, 96, 128, 192 or 256 (backward: up to 192).                                                */
 int sv_stem_patchify_ln_fwd(const float* img, const float* w, const float* b, const float* lnw,
                             const float* lnb, float eps, void* y, int32_t y_dtype, float* mean,
                             float* rstd, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -370,7 +374,8 @@ int sv_resize_u8(const uint8_t* src, const int64_t* desc, const int32_t* coef, i
 
 /* ---- ConvNeXt stage downsample: LayerNorm2d + 2x2/s2 patch gather (GEMM A operand) ------------
  * x [B,H,W,C] f32 -> patches [B*(H/2)*(W/2)][C*4] with k = c*4 + kh*2 + kw (= timm conv weight
- * [2C,C,2,2] flattened), so the Conv2d(k2,s2) is one sv_gemm with b_kmajor=1 on the weight.        */
+ * [2C,C,2,2] flattened), so the Conv2d(k2,s2) is one sv_gemm with b_kmajor=1 on the weight.
+ * C: 96 or 64 * {1, 2, 3, 4, 6, 8, 12, 16}.                                                        */
 int sv_downsample_ln_patch2_fwd(const float* x, const float* lnw, const float* lnb, float eps,
                                 void* patches, int32_t p_dtype, float* mean, float* rstd, int32_t B,
                                 int32_t H, int32_t W, int32_t C, sv_stream_t stream);

@@ -1,5 +1,5 @@
 """ConvNeXt backbone on the gfx950 kernel library -- drop-in for
-``timm.create_model("convnext_{base,large}...", num_classes=0)`` as called at
+``timm.create_model("convnext_{tiny,small,base,large}...", num_classes=0)`` as called at
 spine_vision/training/models/backbone.py:166-170 (timm 1.0.22 ``timm/models/convnext.py``).
 
 * Same module tree and ``state_dict`` keys as timm (``stem.{0,1}``, ``stages.i.downsample.{0,1}``,
@@ -16,6 +16,13 @@ spine_vision/training/models/backbone.py:166-170 (timm 1.0.22 ``timm/models/conv
 * ``precision="bf16"``: bf16 MFMA, bf16 saved activations, f32 residual/gradient streams, f32
   master weights.  ``precision="fp32"``: every tensor f32 and f32 MFMA (parity mode, <=1e-3 vs the
   reference CPU path).
+* ConvNeXt-tiny / small (stage widths 96 / 192 / 384 / 768): 192, 384 and 768 are -large's stages 1-3; the stage-1
+  width C = 96 has kernel forms of its own (LayerNorm over 4-lane rows, the downsample and fused stem over 32-lane
+  rows, the VALU depthwise kernels with a masked half channel group; DESIGN.md "ConvNeXt-tiny/small").  Every
+  block-level choice keyed on C is a set membership that 96 is not in: the fused MLP forward (``fused_mlp_c`` within
+  ``kernels.MLP_FUSED_C``) and backward (``kernels.MLP_BWD_FUSED_C``) and the LayerNorm-in-the-fc1-dgrad epilogue
+  (``kernels.linear_dgrad_ln``: C % 256 == 0) all decline it, so a C = 96 block runs the separate fc1 / fc2 GEMMs and
+  the stand-alone LayerNorm backward.  The weight-gradient schedules (``lean_sync``, side stream) do not depend on C.
 * ConvNeXt V2 (``convnextv2_{base,large}``, timm's Linear-MLP V2 variants): a block has no layer-scale ``gamma``
   and puts Global Response Normalization between GELU and fc2 -- ``mlp.grn.{weight,bias}`` ([4C], zeros at init).
   The state_dict keys are V1's minus ``gamma`` plus those two.  timm is not a dependency of this package, so this is an

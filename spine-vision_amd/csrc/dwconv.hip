@@ -12,6 +12,13 @@
 //
 // The op is HBM-bound (49 FMA per 4-8 bytes moved).
 //
+// Channel counts: C % 32 == 0.  C % 64 == 0 runs the kernels as above.  Otherwise (ConvNeXt-tiny / small's C = 96) the
+// PART instantiations run: the same 64-lane geometry with the last channel group half filled, its lanes >= C - 64 *
+// group MASKED -- their DMA chunks read the zero page (never past the tensor's end), their weight / bias / accumulate
+// loads read the group's first channel, their stores are suppressed.  Chosen over a 32-channel group geometry because
+// the ring, the strip walk and the counted waits stay exactly those of the full groups; the cost is idle lanes only,
+// 32 of every ceil(C / 64) * 64 (25 % of the FMA lanes at C = 96), while the HBM bytes stay those of C channels.
+//
 //   fwd          z = b + sum_tap w[tap] * x[p + tap]               (+ LayerNorm via ln_fwd)
 //   bwd-data     dx = (acc ? dx : 0) + sum_tap w[48 - tap] * dz[p + tap]   (flipped kernel)
 //   bwd-weight   dW[c][tap] = sum_p dz[p,c] * x[p + tap, c],  db[c] = sum_p dz[p,c]
@@ -105,9 +112,11 @@ struct DwRow {
 // DMA the NCOL columns wstart .. wstart+NCOL-1 of row h of the wave's channel group (xg = x + c0,
 // uniform) into dst.  Out-of-image rows / columns, and the columns past NCOL that fill the last
 // instruction, read the zero page, so every row costs the same fixed number of DMAs.
-template <int NCOL, typename T>
+// PART: only the group's first nv channels exist; the 16-B chunks of the others read the zero page too (nv % 32 == 0, so
+// a chunk is whole or absent).
+template <int NCOL, typename T, bool PART = false>
 __device__ __forceinline__ void dma_row(const T* __restrict__ xg, const DwGeo& g, int b, int h, int wstart, int lane,
-                                        char* dst) {
+                                        char* dst, int nv = 64) {
   using R = DwRow<T>;
   const bool okh = h >= 0 && h < g.H;
   const T* rowp = xg + (size_t)((b * g.H + (okh ? h : 0)) * g.W) * g.C;
@@ -116,7 +125,7 @@ __device__ __forceinline__ void dma_row(const T* __restrict__ xg, const DwGeo& g
 #pragma unroll
   for (int d = 0; d < R::template nd<NCOL>(); ++d) {
     const int j = d * R::CPD + jl, w = wstart + j;
-    const bool ok = okh && j < NCOL && w >= 0 && w < g.W;
+    const bool ok = okh && j < NCOL && w >= 0 && w < g.W && (!PART || ch < nv);
     const T* src = ok ? rowp + (size_t)w * g.C + ch : zero + ch;
     __builtin_amdgcn_global_load_lds((const void*)src, (dw_lds_void*)(dst + d * 1024), 16, 0, 0);
   }
@@ -132,7 +141,7 @@ constexpr size_t dw_ring_lds() {
   return (size_t)(kDwThreads / 64) * PF * DwRow<TIN>::template bytes<TW + 6>();
 }
 
-template <int PF, int TW, typename TIN, typename TOUT, bool FLIP, bool ACCUM>
+template <int PF, int TW, typename TIN, typename TOUT, bool FLIP, bool ACCUM, bool PART = false>
 __global__ void __launch_bounds__(kDwThreads) dwconv7_ring_kernel(const TIN* __restrict__ x,
                                                                   const float* __restrict__ wdw,
                                                                   const float* __restrict__ bdw,
@@ -144,10 +153,13 @@ __global__ void __launch_bounds__(kDwThreads) dwconv7_ring_kernel(const TIN* __r
   constexpr int NL = DwRow<TIN>::template nd<TC>();  // DMA instructions per row
   const int lane = threadIdx.x & 63, wv = wave_id_uniform();
   const int gw = xcd_block(blockIdx.x, gridDim.x, g.xcd) * (kDwThreads / 64) + wv;
-  const int ncg = g.C / 64;
+  const int ncg = PART ? (g.C + 63) / 64 : g.C / 64;
   if (gw >= g.ntiles * ncg) return;  // whole wave; no barriers below
   char* ring = dw_smem + wv * PF * ROWB;
-  const int tile = gw % g.ntiles, c0 = (gw / g.ntiles) * 64, c = c0 + lane;
+  const int tile = gw % g.ntiles, c0 = (gw / g.ntiles) * 64;
+  const int nv = PART ? (g.C - c0 < 64 ? g.C - c0 : 64) : 64;  // channels of this group that exist
+  const bool live = !PART || lane < nv;
+  const int c = live ? c0 + lane : c0;  // a masked lane reads the group's first channel's parameters
   int b, h0, w0;
   dw_tile(g, tile, b, h0, w0);
   const TIN* xg = x + c0;
@@ -167,14 +179,15 @@ __global__ void __launch_bounds__(kDwThreads) dwconv7_ring_kernel(const TIN* __r
 #pragma unroll
   for (int o = 0; o < TW; ++o) pcur[o] = pnew[o] = 0.f;
 #pragma unroll
-  for (int p = 0; p < PF - 1; ++p) dma_row<TC>(xg, g, b, h0 - 3 + p, w0 - 3, lane, ring + p * ROWB);
+  for (int p = 0; p < PF - 1; ++p) dma_row<TC, TIN, PART>(xg, g, b, h0 - 3 + p, w0 - 3, lane, ring + p * ROWB, nv);
 #pragma nounroll
   for (int ib = 0; ib < TR; ib += 7) {
 #pragma unroll
     for (int u = 0; u < 7; ++u) {
       const int ir = ib + u;
       if (ir >= TR) break;
-      if (ir + PF - 1 < TR) dma_row<TC>(xg, g, b, h0 - 3 + ir + PF - 1, w0 - 3, lane, ring + ((ir + PF - 1) % PF) * ROWB);
+      if (ir + PF - 1 < TR)
+        dma_row<TC, TIN, PART>(xg, g, b, h0 - 3 + ir + PF - 1, w0 - 3, lane, ring + ((ir + PF - 1) % PF) * ROWB, nv);
       const int rem = TR - 1 - ir;
       wait_rows<PF, NL>(rem < PF - 1 ? rem : PF - 1);
       const char* row = ring + (ir % PF) * ROWB;
@@ -185,7 +198,7 @@ __global__ void __launch_bounds__(kDwThreads) dwconv7_ring_kernel(const TIN* __r
         if (h < g.H) {
           const TOUT* prow = og + ((size_t)b * g.H + h) * g.W * g.C;
 #pragma unroll
-          for (int o = 0; o < TW; ++o) pnew[o] = (w0 + o < g.W) ? ld(prow + (size_t)(w0 + o) * g.C, lane) : 0.f;
+          for (int o = 0; o < TW; ++o) pnew[o] = (w0 + o < g.W && live) ? ld(prow + (size_t)(w0 + o) * g.C, lane) : 0.f;
         }
       }
 #pragma unroll
@@ -206,7 +219,7 @@ __global__ void __launch_bounds__(kDwThreads) dwconv7_ring_kernel(const TIN* __r
           const size_t rbase = ((size_t)b * g.H + h) * g.W;
 #pragma unroll
           for (int o = 0; o < TW; ++o) {
-            if (w0 + o < g.W) {
+            if (w0 + o < g.W && live) {
               const size_t i = (rbase + w0 + o) * g.C;
               const float v = ACCUM ? pcur[o] + acc[sl][o] : acc[sl][o];
               st(og + i, lane, v);
@@ -234,7 +247,7 @@ constexpr size_t dw_wgrad_ring_lds() {
   return (size_t)(kDwThreads / 64) * PF * (DwRow<TIN>::template bytes<TW + 6>() + DwRow<TDZ>::template bytes<TW>());
 }
 
-template <int PF, int TW, typename TDZ, typename TIN>
+template <int PF, int TW, typename TDZ, typename TIN, bool PART = false>
 __global__ void __launch_bounds__(kDwThreads) dwconv7_wgrad_ring_kernel(const TDZ* __restrict__ dz,
                                                                         const TIN* __restrict__ x,
                                                                         float* __restrict__ dw_part,
@@ -246,6 +259,7 @@ __global__ void __launch_bounds__(kDwThreads) dwconv7_wgrad_ring_kernel(const TD
   constexpr int NL = DwRow<TIN>::template nd<TC>() + DwRow<TDZ>::template nd<TW>();
   const int lane = threadIdx.x & 63, wv = wave_id_uniform();
   const int c0 = blockIdx.y * 64;
+  const int nv = PART ? (g.C - c0 < 64 ? g.C - c0 : 64) : 64;  // channels of this group that exist
   const TIN* xg = x + c0;
   const TDZ* dg = dz + c0;
   char* ring = dw_smem + wv * PF * ROWB;
@@ -259,8 +273,8 @@ __global__ void __launch_bounds__(kDwThreads) dwconv7_wgrad_ring_kernel(const TD
     dw_tile(g, tile, b, h0, w0);
     auto issue = [&](int ir) {
       char* slot = ring + (ir % PF) * ROWB;
-      dma_row<TC>(xg, g, b, h0 - 3 + ir, w0 - 3, lane, slot);
-      dma_row<TW>(dg, g, b, ir < TH ? h0 + ir : -1, w0, lane, slot + XB);
+      dma_row<TC, TIN, PART>(xg, g, b, h0 - 3 + ir, w0 - 3, lane, slot, nv);
+      dma_row<TW, TDZ, PART>(dg, g, b, ir < TH ? h0 + ir : -1, w0, lane, slot + XB, nv);
     };
     float dzb[7][TW];
     float in[TC];
@@ -318,9 +332,10 @@ __global__ void __launch_bounds__(kDwThreads) dwconv7_wgrad_ring_kernel(const TD
   }
   for (int i = threadIdx.x; i < 64 * 49; i += kDwThreads) {
     const int ch = i / 49, tap = i - ch * 49;
+    if (PART && ch >= nv) continue;  // the half group's masked lanes hold zeros; their channels do not exist
     dw_part[(size_t)lb * g.C * 49 + (size_t)(c0 + ch) * 49 + tap] = red[tap * 64 + ch];
   }
-  if (threadIdx.x < 64) db_part[(size_t)lb * g.C + c0 + threadIdx.x] = redb[threadIdx.x];
+  if (threadIdx.x < nv) db_part[(size_t)lb * g.C + c0 + threadIdx.x] = redb[threadIdx.x];
 }
 
 // ring depths: f32 input rows (3 KiB for a 4-wide strip) 3 deep, so four workgroups fit a CU as with bf16
@@ -339,7 +354,7 @@ static DwGeo dw_geo(int B, int H, int W, int C) {
   return g;
 }
 
-static int dw_blocks(const DwGeo& g) { return ceil_div((long long)g.ntiles * (g.C / 64), kDwThreads / 64); }
+static int dw_blocks(const DwGeo& g) { return ceil_div((long long)g.ntiles * ((g.C + 63) / 64), kDwThreads / 64); }
 
 // ---------------------------------------------------------------------------------------------
 // Depthwise conv + LayerNorm in ONE pass (timm ConvNeXtBlock: conv_dw -> norm): one workgroup per strip with one wave
@@ -547,7 +562,7 @@ int sv_dwconv7_ln_fwd(const void* x, int32_t x_dtype, const float* wdw, const fl
                       int32_t y_dtype, float* mean, float* rstd, int32_t B, int32_t H, int32_t W,
                       int32_t C, sv_stream_t stream) {
   SV_REQUIRE(x && wdw && bdw && lnw && lnb && y && mean && rstd, "sv_dwconv7_ln_fwd: null pointer");
-  SV_REQUIRE(C % 64 == 0 && C > 0, "sv_dwconv7_ln_fwd: C=%d must be a multiple of 64", C);
+  SV_REQUIRE(C % 32 == 0 && C > 0, "sv_dwconv7_ln_fwd: C=%d must be a positive multiple of 32", C);
   if (B <= 0 || H <= 0 || W <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
   const DwGeo g = dw_geo(B, H, W, C);
@@ -569,15 +584,19 @@ int sv_dwconv7_ln_fwd(const void* x, int32_t x_dtype, const float* wdw, const fl
   }
   SV_REQUIRE(z, "sv_dwconv7_ln_fwd: z == NULL needs the fused form (sv_dwconv7_ln_fused_ok)");
   const int grid = dw_blocks(g);
-#define RLAUNCH(TI, TO)                                                                                       \
-  dwconv7_ring_kernel<dw_pf<TI>(), DW_TW, TI, TO, false, false><<<grid, kDwThreads, dw_ring_lds<dw_pf<TI>(), DW_TW, TI>(), s>>>( \
+  // C % 64 != 0: the masked half-group instantiation (file header); every other C runs the kernels it always ran
+#define RLAUNCH_(TI, TO, PART)                                                                                \
+  dwconv7_ring_kernel<dw_pf<TI>(), DW_TW, TI, TO, false, false, PART><<<grid, kDwThreads, dw_ring_lds<dw_pf<TI>(), DW_TW, TI>(), s>>>( \
       (const TI*)x, wdw, bdw, (TO*)z, nullptr, g)
+#define RLAUNCH(TI, TO) \
+  do { if (C % 64) RLAUNCH_(TI, TO, true); else RLAUNCH_(TI, TO, false); } while (0)
   if (x_dtype == SV_F32 && z_dtype == SV_F32) RLAUNCH(float, float);
   else if (x_dtype == SV_F32 && z_dtype == SV_BF16) RLAUNCH(float, uint16_t);
   else if (x_dtype == SV_BF16 && z_dtype == SV_BF16) RLAUNCH(uint16_t, uint16_t);
   else if (x_dtype == SV_BF16 && z_dtype == SV_F32) RLAUNCH(uint16_t, float);
   else return set_error(SV_ERR_INVALID_ARG, "sv_dwconv7_ln_fwd: bad dtype");
 #undef RLAUNCH
+#undef RLAUNCH_
   int rc = check_launch("sv_dwconv7_ln_fwd(dwconv)");
   if (rc) return rc;
   return sv_layernorm_fwd(z, z_dtype, lnw, lnb, y, y_dtype, mean, rstd, (int64_t)B * H * W, C, eps, stream);
@@ -592,28 +611,31 @@ int sv_dwconv7_ln_fused_ok(int32_t B, int32_t H, int32_t W, int32_t C, int32_t x
 int sv_dwconv7_bwd_data(const void* dz, int32_t dz_dtype, const float* wdw, float* dx, uint16_t* dx_bf16,
                         int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, sv_stream_t stream) {
   SV_REQUIRE(dz && wdw && dx, "sv_dwconv7_bwd_data: null pointer");
-  SV_REQUIRE(C % 64 == 0 && C > 0, "sv_dwconv7_bwd_data: C=%d must be a multiple of 64", C);
+  SV_REQUIRE(C % 32 == 0 && C > 0, "sv_dwconv7_bwd_data: C=%d must be a positive multiple of 32", C);
   SV_REQUIRE(dz != (const void*)dx, "sv_dwconv7_bwd_data: dz and dx must not alias");
   SV_REQUIRE(dz_dtype == SV_F32 || dz_dtype == SV_BF16, "sv_dwconv7_bwd_data: bad dz dtype");
   if (B <= 0 || H <= 0 || W <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
   const DwGeo g = dw_geo(B, H, W, C);
   const int grid = dw_blocks(g);
-#define RBWD(TD, ACC)                                                                                             \
-  dwconv7_ring_kernel<dw_pf<TD>(), DW_TW, TD, float, true, ACC><<<grid, kDwThreads, dw_ring_lds<dw_pf<TD>(), DW_TW, TD>(), s>>>( \
+#define RBWD_(TD, ACC, PART)                                                                                      \
+  dwconv7_ring_kernel<dw_pf<TD>(), DW_TW, TD, float, true, ACC, PART><<<grid, kDwThreads, dw_ring_lds<dw_pf<TD>(), DW_TW, TD>(), s>>>( \
       (const TD*)dz, wdw, nullptr, dx, dx_bf16, g)
+#define RBWD(TD, ACC) \
+  do { if (C % 64) RBWD_(TD, ACC, true); else RBWD_(TD, ACC, false); } while (0)
   if (dz_dtype == SV_F32) {
     if (accumulate) RBWD(float, true); else RBWD(float, false);
   } else {
     if (accumulate) RBWD(uint16_t, true); else RBWD(uint16_t, false);
   }
 #undef RBWD
+#undef RBWD_
   return check_launch("sv_dwconv7_bwd_data");
 }
 
 int sv_dwconv7_bwd_weight_nparts(int32_t B, int32_t H, int32_t W, int32_t C) {
   const DwGeo g = dw_geo(B, H, W, C);
-  const int ncg = C / 64 > 0 ? C / 64 : 1;
+  const int ncg = C > 0 ? (C + 63) / 64 : 1;  // channel groups, the last one half filled when C % 64 == 32
   // ~1024 workgroups (4096 waves, about 4 workgroups per CU) over all channel groups: with the 2-row ring a
   // wave has only ~6 KiB in flight, so the HBM latency is hidden by waves per CU (round 3, tools/dw_bench.py:
   // 512 -> 1024 workgroups S1 143 -> 129 us, S2 72 -> 62, S3 37.7 -> 33.2 (bf16 dz), S4 equal; 2048 no
@@ -634,19 +656,23 @@ int sv_dwconv7_bwd_weight(const void* dz, int32_t dz_dtype, const void* x, int32
                           float* db_part, int32_t B, int32_t H, int32_t W, int32_t C,
                           sv_stream_t stream) {
   SV_REQUIRE(dz && x && dw_part && db_part, "sv_dwconv7_bwd_weight: null pointer");
-  SV_REQUIRE(C % 64 == 0 && C > 0, "sv_dwconv7_bwd_weight: C=%d must be a multiple of 64", C);
+  SV_REQUIRE(C % 32 == 0 && C > 0, "sv_dwconv7_bwd_weight: C=%d must be a positive multiple of 32", C);
   SV_REQUIRE((dz_dtype == SV_F32 || dz_dtype == SV_BF16) && (x_dtype == SV_F32 || x_dtype == SV_BF16),
              "sv_dwconv7_bwd_weight: bad dtype");
   if (B <= 0 || H <= 0 || W <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
   const DwGeo g = dw_geo(B, H, W, C);
-  const dim3 grid(sv_dwconv7_bwd_weight_nparts(B, H, W, C), C / 64);
+  const dim3 grid(sv_dwconv7_bwd_weight_nparts(B, H, W, C), (C + 63) / 64);
   constexpr size_t red_bytes = (49 * 64 + 64) * sizeof(float);
 #define RWG(TD, TX)                                                                                            \
   {                                                                                                            \
     constexpr size_t ring = dw_wgrad_ring_lds<DW_WGRAD_PF, DW_TW, TD, TX>();                                   \
-    dwconv7_wgrad_ring_kernel<DW_WGRAD_PF, DW_TW, TD, TX><<<grid, kDwThreads, ring > red_bytes ? ring : red_bytes, s>>>( \
-        (const TD*)dz, (const TX*)x, dw_part, db_part, g);                                                     \
+    if (C % 64)                                                                                                \
+      dwconv7_wgrad_ring_kernel<DW_WGRAD_PF, DW_TW, TD, TX, true><<<grid, kDwThreads, ring > red_bytes ? ring : red_bytes, s>>>( \
+          (const TD*)dz, (const TX*)x, dw_part, db_part, g);                                                   \
+    else                                                                                                       \
+      dwconv7_wgrad_ring_kernel<DW_WGRAD_PF, DW_TW, TD, TX><<<grid, kDwThreads, ring > red_bytes ? ring : red_bytes, s>>>( \
+          (const TD*)dz, (const TX*)x, dw_part, db_part, g);                                                   \
   }
   if (dz_dtype == SV_F32 && x_dtype == SV_F32) RWG(float, float)
   else if (dz_dtype == SV_F32) RWG(float, uint16_t)

@@ -131,10 +131,12 @@ __global__ void __launch_bounds__(kLnThreads) ln_bwd_kernel(const TDY* __restric
 
 
 // ------------------------------------------------------------------------------------------
-// Vectorised LayerNorm for C = 8 * LPR * NV with LPR in {8, 16, 32, 64}: every lane owns NV runs of
+// Vectorised LayerNorm for C = 8 * LPR * NV with LPR in {4, 8, 16, 32, 64}: every lane owns NV runs of
 // 8 consecutive channels (one 16-B bf16 / two 16-B f32 accesses per run), a row is spread over LPR
 // lanes, a wave covers 64/LPR rows at once.  ConvNeXt-base's C = 128/256/512/1024 and ConvNeXt-large's
-// 192/384/768/1536 all fit; the per-lane-channel kernels above serve the other widths.
+// 192/384/768/1536 all fit; ConvNeXt-tiny / small's C = 96 is 4 lanes x 24 channels (NV = 3, 16 rows per
+// wave; C = 32 and 160 are the NV = 1 and 5 forms of the same quad), its statistics a two-step DPP quad
+// butterfly.  The per-lane-channel kernels above serve the other widths.
 template <typename T>
 __device__ __forceinline__ void ld8v(const T* __restrict__ p, float (&v)[8]) {
   if constexpr (sizeof(T) == 4) {
@@ -169,6 +171,10 @@ template <int LPR>
 __device__ __forceinline__ float group_sum(float v) {
   if constexpr (SV_LN_XLANE && LPR >= 16) {
     return xlane_group_sum<LPR>(v);
+  } else if constexpr (SV_LN_XLANE && LPR == 4) {
+    v += xlane_xor<2>(v);  // a quad: the two DPP quad permutations are the exact xor partners
+    v += xlane_xor<1>(v);
+    return v;
   } else {
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -335,12 +341,13 @@ __global__ void __launch_bounds__(kLnThreads) ln_bwd_vec_kernel(const TDY* __res
   }
 }
 
-// fast-path geometry: C = 8 * LPR * NV; returns LPR*16+NV or 0.  ConvNeXt-base 128..1024 (NV 1, 2, 4)
-// and ConvNeXt-large 192/384/768/1536 (NV 3 over LPR 8/16/32/64 lanes)
+// fast-path geometry: C = 8 * LPR * NV; returns LPR*16+NV or 0.  ConvNeXt-base 128..1024 (NV 1, 2, 4),
+// ConvNeXt-large 192/384/768/1536 (NV 3 over LPR 8/16/32/64 lanes), ConvNeXt-tiny 96 (NV 3 over a quad)
 static int ln_vec_kind(int C) {
   if (C % 8) return 0;
   const int u = C / 8;
   if (u == 16 || u == 32 || u == 64) return u * 16 + 1;
+  if (u == 4 || u == 12 || u == 20) return 4 * 16 + u / 4;  // C = 32 / 96 / 160: 4 lanes per row, 16 rows per wave
   if (u == 128) return 64 * 16 + 2;
   if (u == 256) return 64 * 16 + 4;
   if (u % 3 == 0 && (u / 3 == 8 || u / 3 == 16 || u / 3 == 32 || u / 3 == 64)) return (u / 3) * 16 + 3;
@@ -353,6 +360,9 @@ static int ln_vec_kind(int C) {
     case 64 * 16 + 1: { constexpr int LPR = 64, NV = 1; __VA_ARGS__; } break; \
     case 64 * 16 + 2: { constexpr int LPR = 64, NV = 2; __VA_ARGS__; } break; \
     case 64 * 16 + 4: { constexpr int LPR = 64, NV = 4; __VA_ARGS__; } break; \
+    case 4 * 16 + 1: { constexpr int LPR = 4, NV = 1; __VA_ARGS__; } break;   \
+    case 4 * 16 + 3: { constexpr int LPR = 4, NV = 3; __VA_ARGS__; } break;   \
+    case 4 * 16 + 5: { constexpr int LPR = 4, NV = 5; __VA_ARGS__; } break;   \
     case 8 * 16 + 3: { constexpr int LPR = 8, NV = 3; __VA_ARGS__; } break;   \
     case 16 * 16 + 3: { constexpr int LPR = 16, NV = 3; __VA_ARGS__; } break; \
     case 32 * 16 + 3: { constexpr int LPR = 32, NV = 3; __VA_ARGS__; } break; \
@@ -695,6 +705,308 @@ __global__ void __launch_bounds__(kLnThreads) ds_bwd_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
+// 32-lane row groups: the C = 32 * K forms of the downsample and the fused stem for widths that are no multiple of
+// 64 (ConvNeXt-tiny / small's C = 96, K = 3).  A wave holds TWO rows (patches / pixels), one per 32-lane half;
+// lane l of a half owns channels c = l + 32 t, so every lane is busy for the whole row and a half's access is 128
+// contiguous bytes.  The statistics are the 32-lane butterfly (group_sum<32>).  The second half's row may lie past
+// the end: it then re-reads the first half's row (in bounds) and its stores and gradient contributions are dropped.
+template <typename TP, int K>
+__global__ void __launch_bounds__(kLnThreads) ds_fwd_g32_kernel(const float* __restrict__ x,
+                                                                const float* __restrict__ lnw,
+                                                                const float* __restrict__ lnb, float eps,
+                                                                TP* __restrict__ patches, float* __restrict__ mean,
+                                                                float* __restrict__ rstd, int B, int H, int W, int C) {
+  const int lane = threadIdx.x & 63, l = lane & 31, sub = lane >> 5;
+  const int64_t wave = (int64_t)blockIdx.x * (kLnThreads / 64) + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * (kLnThreads / 64);
+  const int Ho = H / 2, Wo = W / 2;
+  const int64_t np = (int64_t)B * Ho * Wo;
+  const float invC = 1.0f / (float)C;
+  float gw[K], gb[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    gw[t] = lnw[l + 32 * t];
+    gb[t] = lnb[l + 32 * t];
+  }
+  for (int64_t p0 = wave * 2; p0 < np; p0 += nwaves * 2) {
+    const bool ok = p0 + sub < np;
+    const int64_t p = ok ? p0 + sub : p0;
+    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho), b = (int)(p / ((int64_t)Wo * Ho));
+    float v[4][K];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float* xr = x + (size_t)(((int64_t)b * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1)) * C;
+#pragma unroll
+      for (int t = 0; t < K; ++t) v[q][t] = xr[l + 32 * t];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t pix = ((int64_t)b * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1);
+      float s = 0.f;
+#pragma unroll
+      for (int t = 0; t < K; ++t) s += v[q][t];
+      const float mu = group_sum<32>(s) * invC;
+      float qq = 0.f;
+#pragma unroll
+      for (int t = 0; t < K; ++t) qq += (v[q][t] - mu) * (v[q][t] - mu);
+      const float rs = rsqrtf(group_sum<32>(qq) * invC + eps);
+#pragma unroll
+      for (int t = 0; t < K; ++t) v[q][t] = (v[q][t] - mu) * rs * gw[t] + gb[t];
+      if (l == 0 && ok) {
+        mean[pix] = mu;
+        rstd[pix] = rs;
+      }
+    }
+    if (ok) {
+#pragma unroll
+      for (int t = 0; t < K; ++t)
+        st4(patches, (size_t)p * 4 * C + 4 * (l + 32 * t), make_float4(v[0][t], v[1][t], v[2][t], v[3][t]));
+    }
+  }
+}
+
+template <int K>
+__global__ void __launch_bounds__(kLnThreads) ds_bwd_g32_kernel(
+    const float* __restrict__ dpatches, const float* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ lnw, float* __restrict__ dx,
+    uint16_t* __restrict__ dx_bf16, float* __restrict__ dlnw_part, float* __restrict__ dlnb_part, int B, int H,
+    int W, int C) {
+  __shared__ float red[2][kLnThreads / 64][2][32 * K];  // [dw | db][wave][half][channel]
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l = lane & 31, sub = lane >> 5;
+  const int64_t wave = (int64_t)blockIdx.x * (kLnThreads / 64) + wid;
+  const int64_t nwaves = (int64_t)gridDim.x * (kLnThreads / 64);
+  const int Ho = H / 2, Wo = W / 2;
+  const int64_t np = (int64_t)B * Ho * Wo;
+  const float invC = 1.0f / (float)C;
+  float wr[K], adw[K], adb[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    wr[t] = lnw[l + 32 * t];
+    adw[t] = adb[t] = 0.f;
+  }
+  for (int64_t p0 = wave * 2; p0 < np; p0 += nwaves * 2) {
+    const bool ok = p0 + sub < np;
+    const int64_t p = ok ? p0 + sub : p0;
+    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho), b = (int)(p / ((int64_t)Wo * Ho));
+    float dq[4][K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+      const float4 d4 = *reinterpret_cast<const float4*>(dpatches + (size_t)p * 4 * C + 4 * (l + 32 * t));
+      dq[0][t] = ok ? d4.x : 0.f; dq[1][t] = ok ? d4.y : 0.f; dq[2][t] = ok ? d4.z : 0.f; dq[3][t] = ok ? d4.w : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t pix = ((int64_t)b * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1);
+      const float mu = mean[pix], rs = rstd[pix];
+      float xh[K], g[K], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int t = 0; t < K; ++t) {
+        xh[t] = (x[(size_t)pix * C + l + 32 * t] - mu) * rs;
+        g[t] = dq[q][t] * wr[t];
+        s1 += g[t];
+        s2 += g[t] * xh[t];
+        adw[t] += dq[q][t] * xh[t];
+        adb[t] += dq[q][t];
+      }
+      s1 = group_sum<32>(s1) * invC;
+      s2 = group_sum<32>(s2) * invC;
+      if (ok) {
+#pragma unroll
+        for (int t = 0; t < K; ++t) {
+          const size_t o = (size_t)pix * C + l + 32 * t;
+          const float v = rs * (g[t] - s1 - xh[t] * s2);
+          dx[o] = v;
+          if (dx_bf16) dx_bf16[o] = f2bf(v);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    red[0][wid][sub][l + 32 * t] = adw[t];
+    red[1][wid][sub][l + 32 * t] = adb[t];
+  }
+  __syncthreads();
+  // fixed order: waves 0..3, first half then second
+  for (int c = threadIdx.x; c < C; c += kLnThreads) {
+    float sw = 0.f, sb = 0.f;
+#pragma unroll
+    for (int k = 0; k < kLnThreads / 64; ++k) {
+      sw += red[0][k][0][c];
+      sw += red[0][k][1][c];
+      sb += red[1][k][0][c];
+      sb += red[1][k][1][c];
+    }
+    dlnw_part[(size_t)blockIdx.x * C + c] = sw;
+    dlnb_part[(size_t)blockIdx.x * C + c] = sb;
+  }
+}
+
+// fused stem, two output pixels per wave: lanes 0..47 load both 48-value patches, v_readlane broadcasts value k of
+// each and a select per k picks the half's own, so the 48 * K FMAs per lane run on all 64 lanes
+template <typename TY, int K>
+__global__ void __launch_bounds__(64 * kStemWaves) stem_fwd_g32_kernel(
+    const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
+    const float* __restrict__ lnw, const float* __restrict__ lnb, float eps, TY* __restrict__ y,
+    float* __restrict__ mean, float* __restrict__ rstd, int B, int H, int W, int C) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* wl = smem;                       // [48][C]
+  for (int i = threadIdx.x; i < 48 * C; i += blockDim.x) {
+    const int c = i % C, k = i / C;
+    wl[i] = w[(size_t)c * 48 + k];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l = lane & 31, sub = lane >> 5;
+  const int Ho = H / 4, Wo = W / 4;
+  const int64_t npix = (int64_t)B * Ho * Wo;
+  const float invC = 1.0f / (float)C;
+  float bb[K], gw[K], gb[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    bb[t] = bias[l + 32 * t];
+    gw[t] = lnw[l + 32 * t];
+    gb[t] = lnb[l + 32 * t];
+  }
+  auto patch = [&](int64_t p) {
+    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho), b = (int)(p / ((int64_t)Wo * Ho));
+    const int ci = lane >> 4, kh = (lane >> 2) & 3, kw = lane & 3;
+    return lane < 48 ? img[(((size_t)b * 3 + ci) * H + (4 * i + kh)) * W + (4 * j + kw)] : 0.f;
+  };
+  for (int64_t p0 = ((int64_t)blockIdx.x * kStemWaves + wid) * 2; p0 < npix; p0 += (int64_t)gridDim.x * kStemWaves * 2) {
+    const bool two = p0 + 1 < npix;  // wave-uniform
+    const float pa = patch(p0), pb = patch(two ? p0 + 1 : p0);
+    const bool ok = sub == 0 || two;
+    const int64_t p = p0 + (two ? sub : 0);
+    float z[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) z[t] = bb[t];
+#pragma unroll
+    for (int k = 0; k < 48; ++k) {
+      const float va = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pa), k));
+      const float vb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pb), k));
+      const float pv = sub ? vb : va;
+#pragma unroll
+      for (int t = 0; t < K; ++t) z[t] = fmaf(wl[k * C + l + 32 * t], pv, z[t]);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < K; ++t) s += z[t];
+    const float mu = group_sum<32>(s) * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int t = 0; t < K; ++t) q += (z[t] - mu) * (z[t] - mu);
+    const float rs = rsqrtf(group_sum<32>(q) * invC + eps);
+    if (ok) {
+#pragma unroll
+      for (int t = 0; t < K; ++t) st(y, (size_t)p * C + l + 32 * t, (z[t] - mu) * rs * gw[t] + gb[t]);
+      if (l == 0) {
+        mean[p] = mu;
+        rstd[p] = rs;
+      }
+    }
+  }
+}
+
+template <int K>
+__global__ void __launch_bounds__(64 * kStemWaves) stem_bwd_g32_kernel(
+    const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
+    const float* __restrict__ lnw, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ dy, float* __restrict__ dw_part, float* __restrict__ db_part,
+    float* __restrict__ dlnw_part, float* __restrict__ dlnb_part, int B, int H, int W, int C) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* wl = smem;                 // [48][C]
+  float* comb = smem + 48 * C;      // [48*C + 3*C] combine buffer
+  for (int i = threadIdx.x; i < 48 * C; i += blockDim.x) {
+    const int c = i % C, k = i / C;
+    wl[i] = w[(size_t)c * 48 + k];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l = lane & 31, sub = lane >> 5;
+  const int Ho = H / 4, Wo = W / 4;
+  const int64_t npix = (int64_t)B * Ho * Wo;
+  const float invC = 1.0f / (float)C;
+  float bb[K], gw[K];
+  float adw[K][48], adb[K], adlw[K], adlb[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    bb[t] = bias[l + 32 * t];
+    gw[t] = lnw[l + 32 * t];
+    adb[t] = adlw[t] = adlb[t] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 48; ++k) adw[t][k] = 0.f;
+  }
+  auto patch = [&](int64_t p) {
+    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho), b = (int)(p / ((int64_t)Wo * Ho));
+    const int ci = lane >> 4, kh = (lane >> 2) & 3, kw = lane & 3;
+    return lane < 48 ? img[(((size_t)b * 3 + ci) * H + (4 * i + kh)) * W + (4 * j + kw)] : 0.f;
+  };
+  for (int64_t p0 = ((int64_t)blockIdx.x * kStemWaves + wid) * 2; p0 < npix; p0 += (int64_t)gridDim.x * kStemWaves * 2) {
+    const bool two = p0 + 1 < npix;  // wave-uniform
+    const float pa = patch(p0), pb = patch(two ? p0 + 1 : p0);
+    const bool ok = sub == 0 || two;
+    const int64_t p = p0 + (two ? sub : 0);
+    float pk[48];
+#pragma unroll
+    for (int k = 0; k < 48; ++k) {
+      const float va = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pa), k));
+      const float vb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pb), k));
+      pk[k] = sub ? vb : va;
+    }
+    const float mu = mean[p], rs = rstd[p];
+    float xh[K], g[K], d[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+      float z = bb[t];
+#pragma unroll
+      for (int k = 0; k < 48; ++k) z = fmaf(wl[k * C + l + 32 * t], pk[k], z);
+      xh[t] = (z - mu) * rs;
+      d[t] = ok ? dy[(size_t)p * C + l + 32 * t] : 0.f;  // a repeated pixel contributes nothing
+      g[t] = d[t] * gw[t];
+    }
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+      s1 += g[t];
+      s2 += g[t] * xh[t];
+    }
+    s1 = group_sum<32>(s1) * invC;
+    s2 = group_sum<32>(s2) * invC;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+      const float dz = rs * (g[t] - s1 - xh[t] * s2);
+      adb[t] += dz;
+      adlw[t] += d[t] * xh[t];
+      adlb[t] += d[t];
+#pragma unroll
+      for (int k = 0; k < 48; ++k) adw[t][k] = fmaf(dz, pk[k], adw[t][k]);
+    }
+  }
+  // deterministic combine of the 8 half-waves (fixed order), layout [C][48] + db + dlnw + dlnb
+  const int nw = 48 * C + 3 * C;
+  for (int hv = 0; hv < 2 * kStemWaves; ++hv) {
+    if (wid * 2 + sub == hv) {
+#pragma unroll
+      for (int t = 0; t < K; ++t) {
+        const int c = l + 32 * t;
+#pragma unroll
+        for (int k = 0; k < 48; ++k) comb[c * 48 + k] = (hv ? comb[c * 48 + k] : 0.f) + adw[t][k];
+        comb[48 * C + c] = (hv ? comb[48 * C + c] : 0.f) + adb[t];
+        comb[49 * C + c] = (hv ? comb[49 * C + c] : 0.f) + adlw[t];
+        comb[50 * C + c] = (hv ? comb[50 * C + c] : 0.f) + adlb[t];
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < nw; i += blockDim.x) {
+    const float v = comb[i];
+    if (i < 48 * C) dw_part[(size_t)blockIdx.x * 48 * C + i] = v;
+    else if (i < 49 * C) db_part[(size_t)blockIdx.x * C + (i - 48 * C)] = v;
+    else if (i < 50 * C) dlnw_part[(size_t)blockIdx.x * C + (i - 49 * C)] = v;
+    else dlnb_part[(size_t)blockIdx.x * C + (i - 50 * C)] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Head: global average pool over HW, then LayerNorm over C.
 //   pool_sum_kernel   grid (C/64, B): 4 waves split the HW rows of one 64-channel group of one
 //                     image (256-B coalesced row reads, 8 in flight per lane), LDS fold -> pooled
@@ -823,7 +1135,7 @@ int sv_layernorm_fwd(const void* x, int32_t x_dtype, const float* w, const float
                      int32_t y_dtype, float* mean, float* rstd, int64_t rows, int32_t C, float eps,
                      sv_stream_t stream) {
   SV_REQUIRE(x && w && b && y && mean && rstd, "sv_layernorm_fwd: null pointer");
-  SV_REQUIRE(ln_vec_kind(C) || cpl_ok(C), "sv_layernorm_fwd: C=%d must be 64*{1,2,3,4,6,8,12,16,24} or 2048", C);
+  SV_REQUIRE(ln_vec_kind(C) || cpl_ok(C), "sv_layernorm_fwd: C=%d must be 32, 96, 160, 64*{1,2,3,4,6,8,12,16,24} or 2048", C);
   if (rows <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
   if (const int kind = ln_vec_kind(C)) {
@@ -860,7 +1172,7 @@ int sv_layernorm_bwd(const void* dy, int32_t dy_dtype, const void* x, int32_t x_
                      const float* rstd, const float* w, void* dx, int32_t dx_dtype, int32_t accumulate,
                      float* dw_part, float* db_part, int64_t rows, int32_t C, sv_stream_t stream) {
   SV_REQUIRE(dy && x && mean && rstd && w && dx && dw_part && db_part, "sv_layernorm_bwd: null pointer");
-  SV_REQUIRE(ln_vec_kind(C) || (cpl_ok(C) && C <= 2048), "sv_layernorm_bwd: C=%d unsupported", C);
+  SV_REQUIRE(ln_vec_kind(C) || (cpl_ok(C) && C <= 2048), "sv_layernorm_bwd: C=%d must be 32, 96, 160, 64*{1,2,3,4,6,8,12,16,24} or 2048", C);
   if (rows <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
   if (const int kind = ln_vec_kind(C)) {
@@ -902,9 +1214,11 @@ int sv_layernorm_bwd(const void* dy, int32_t dy_dtype, const void* x, int32_t x_
   return check_launch("sv_layernorm_bwd");
 }
 
-static int stem_grid(int B, int H, int W) {
+// C % 64 != 0 (the 32-lane-group kernels): a wave takes two pixels
+static int stem_grid(int B, int H, int W, int C) {
   const int64_t np = (int64_t)B * (H / 4) * (W / 4);
-  const int64_t g = (np + kStemWaves - 1) / kStemWaves;
+  const int ppb = kStemWaves * (C % 64 ? 2 : 1);
+  const int64_t g = (np + ppb - 1) / ppb;
   return (int)(g < 2048 ? (g < 1 ? 1 : g) : 2048);
 }
 
@@ -914,11 +1228,19 @@ int sv_stem_patchify_ln_fwd(const float* img, const float* w, const float* b, co
                             sv_stream_t stream) {
   SV_REQUIRE(img && w && b && lnw && lnb && y && mean && rstd, "sv_stem_patchify_ln_fwd: null pointer");
   SV_REQUIRE(H % 4 == 0 && W % 4 == 0, "sv_stem_patchify_ln_fwd: H,W must be multiples of 4");
-  SV_REQUIRE(C % 64 == 0 && C <= 256, "sv_stem_patchify_ln_fwd: C=%d unsupported", C);
+  SV_REQUIRE(C == 96 || (C > 0 && C % 64 == 0 && C <= 256), "sv_stem_patchify_ln_fwd: C=%d must be 64, 96, 128, 192 or 256", C);
   if (B <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)(48 * C) * sizeof(float);
-  const int grid = stem_grid(B, H, W);
+  const int grid = stem_grid(B, H, W, C);
+#define LAUNCH96(TY) stem_fwd_g32_kernel<TY, 3><<<grid, 64 * kStemWaves, lds, s>>>(img, w, b, lnw, lnb, eps, (TY*)y, mean, rstd, B, H, W, C)
+  if (C == 96) {
+    if (y_dtype == SV_F32) LAUNCH96(float);
+    else if (y_dtype == SV_BF16) LAUNCH96(uint16_t);
+    else return set_error(SV_ERR_INVALID_ARG, "sv_stem_patchify_ln_fwd: bad dtype");
+    return check_launch("sv_stem_patchify_ln_fwd");
+  }
+#undef LAUNCH96
 #define LAUNCH(TY)                                                                              \
   switch (C / 64) {                                                                             \
     case 1: stem_fwd_kernel<TY, 1><<<grid, 64 * kStemWaves, lds, s>>>(img, w, b, lnw, lnb, eps, (TY*)y, mean, rstd, B, H, W, C); break; \
@@ -934,8 +1256,7 @@ int sv_stem_patchify_ln_fwd(const float* img, const float* w, const float* b, co
 }
 
 int sv_stem_patchify_ln_bwd_nparts(int32_t B, int32_t H, int32_t W, int32_t C) {
-  (void)C;
-  const int g = stem_grid(B, H, W);
+  const int g = stem_grid(B, H, W, C);
   return g < kStemBwdBlocks ? g : kStemBwdBlocks;
 }
 
@@ -946,11 +1267,15 @@ int sv_stem_patchify_ln_bwd(const float* img, const float* w, const float* b, co
   SV_REQUIRE(img && w && b && lnw && mean && rstd && dy && dw_part && db_part && dlnw_part && dlnb_part,
              "sv_stem_patchify_ln_bwd: null pointer");
   SV_REQUIRE(H % 4 == 0 && W % 4 == 0, "sv_stem_patchify_ln_bwd: H,W must be multiples of 4");
-  SV_REQUIRE(C % 64 == 0 && C <= 192, "sv_stem_patchify_ln_bwd: C=%d unsupported", C);
+  SV_REQUIRE(C == 96 || (C > 0 && C % 64 == 0 && C <= 192), "sv_stem_patchify_ln_bwd: C=%d must be 64, 96, 128 or 192", C);
   if (B <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
   const int grid = sv_stem_patchify_ln_bwd_nparts(B, H, W, C);
   const size_t lds = (size_t)(48 * C + 51 * C) * sizeof(float);
+  if (C == 96) {
+    stem_bwd_g32_kernel<3><<<grid, 64 * kStemWaves, lds, s>>>(img, w, b, lnw, mean, rstd, dy, dw_part, db_part, dlnw_part, dlnb_part, B, H, W, C);
+    return check_launch("sv_stem_patchify_ln_bwd");
+  }
   switch (C / 64) {
     case 1: stem_bwd_kernel<1><<<grid, 64 * kStemWaves, lds, s>>>(img, w, b, lnw, mean, rstd, dy, dw_part, db_part, dlnw_part, dlnb_part, B, H, W, C); break;
     case 2: stem_bwd_kernel<2><<<grid, 64 * kStemWaves, lds, s>>>(img, w, b, lnw, mean, rstd, dy, dw_part, db_part, dlnw_part, dlnb_part, B, H, W, C); break;
@@ -959,9 +1284,11 @@ int sv_stem_patchify_ln_bwd(const float* img, const float* w, const float* b, co
   return check_launch("sv_stem_patchify_ln_bwd");
 }
 
-static int ds_grid(int B, int H, int W) {
+// C % 64 != 0 (the 32-lane-group kernels): a wave takes two patches
+static int ds_grid(int B, int H, int W, int C) {
   const int64_t np = (int64_t)B * (H / 2) * (W / 2);
-  const int64_t g = (np + 3) / 4;
+  const int ppb = (kLnThreads / 64) * (C % 64 ? 2 : 1);
+  const int64_t g = (np + ppb - 1) / ppb;
   return (int)(g < 1024 ? (g < 1 ? 1 : g) : 1024);
 }
 
@@ -970,10 +1297,18 @@ int sv_downsample_ln_patch2_fwd(const float* x, const float* lnw, const float* l
                                 int32_t H, int32_t W, int32_t C, sv_stream_t stream) {
   SV_REQUIRE(x && lnw && lnb && patches && mean && rstd, "sv_downsample_ln_patch2_fwd: null pointer");
   SV_REQUIRE(H % 2 == 0 && W % 2 == 0, "sv_downsample_ln_patch2_fwd: H,W must be even");
-  SV_REQUIRE(cpl_ok(C) && C <= 1024, "sv_downsample_ln_patch2_fwd: C=%d unsupported", C);
+  SV_REQUIRE(C == 96 || (cpl_ok(C) && C <= 1024), "sv_downsample_ln_patch2_fwd: C=%d must be 96 or 64*{1,2,3,4,6,8,12,16}", C);
   if (B <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ds_grid(B, H, W);
+  const int grid = ds_grid(B, H, W, C);
+  if (C == 96) {
+    if (p_dtype == SV_F32)
+      ds_fwd_g32_kernel<float, 3><<<grid, kLnThreads, 0, s>>>(x, lnw, lnb, eps, (float*)patches, mean, rstd, B, H, W, C);
+    else if (p_dtype == SV_BF16)
+      ds_fwd_g32_kernel<uint16_t, 3><<<grid, kLnThreads, 0, s>>>(x, lnw, lnb, eps, (uint16_t*)patches, mean, rstd, B, H, W, C);
+    else return set_error(SV_ERR_INVALID_ARG, "sv_downsample_ln_patch2_fwd: bad dtype");
+    return check_launch("sv_downsample_ln_patch2_fwd");
+  }
   if (p_dtype == SV_F32) {
     SV_CPL_SWITCH(C / 64, ds_fwd_kernel<float, CPL><<<grid, kLnThreads, 0, s>>>(
                               x, lnw, lnb, eps, (float*)patches, mean, rstd, B, H, W, C));
@@ -987,8 +1322,7 @@ int sv_downsample_ln_patch2_fwd(const float* x, const float* lnw, const float* l
 }
 
 int sv_downsample_ln_patch2_bwd_nparts(int32_t B, int32_t H, int32_t W, int32_t C) {
-  (void)C;
-  return ds_grid(B, H, W);
+  return ds_grid(B, H, W, C);
 }
 
 int sv_downsample_ln_patch2_bwd(const float* dpatches, const float* x, const float* mean,
@@ -997,10 +1331,14 @@ int sv_downsample_ln_patch2_bwd(const float* dpatches, const float* x, const flo
                                 sv_stream_t stream) {
   SV_REQUIRE(dpatches && x && mean && rstd && lnw && dx && dlnw_part && dlnb_part,
              "sv_downsample_ln_patch2_bwd: null pointer");
-  SV_REQUIRE(cpl_ok(C) && C <= 1024, "sv_downsample_ln_patch2_bwd: C=%d unsupported", C);
+  SV_REQUIRE(C == 96 || (cpl_ok(C) && C <= 1024), "sv_downsample_ln_patch2_bwd: C=%d must be 96 or 64*{1,2,3,4,6,8,12,16}", C);
   if (B <= 0) return SV_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ds_grid(B, H, W);
+  const int grid = ds_grid(B, H, W, C);
+  if (C == 96) {
+    ds_bwd_g32_kernel<3><<<grid, kLnThreads, 0, s>>>(dpatches, x, mean, rstd, lnw, dx, dx_bf16, dlnw_part, dlnb_part, B, H, W, C);
+    return check_launch("sv_downsample_ln_patch2_bwd");
+  }
   SV_CPL_SWITCH(C / 64, ds_bwd_kernel<CPL><<<grid, kLnThreads, 0, s>>>(
                             dpatches, x, mean, rstd, lnw, dx, dx_bf16, dlnw_part, dlnb_part, B, H, W, C));
   return check_launch("sv_downsample_ln_patch2_bwd");

@@ -788,7 +788,7 @@ def dwconv7_ln_fwd(x4d, wdw, bdw, lnw, lnb, *, act_dtype, eps=EPS_LN, save_z=Tru
     runs), y = LN(z), mean, rstd.  C = 128 / 256 / 512 over an f32 input run as ONE kernel (sv_dwconv7_ln_fused_ok),
     bitwise the two-launch result."""
     B, H, W, C = x4d.shape
-    _check(C % 64 == 0, "dwconv7: C must be a multiple of 64")
+    _check(C % 32 == 0, "dwconv7: C must be a multiple of 32")
     if DW_MFMA and act_dtype == torch.bfloat16:
         z = dwconv7_fwd_mfma(x4d, wdw, bdw)
         y, mean, rstd = layernorm_fwd(z.view(-1, C), lnw, lnb, out_dtype=act_dtype, eps=eps)

@@ -3,10 +3,10 @@
 (backbone.py:166-170) and returns ``(module, module.num_features)``.
 
 Here ``create`` returns the MI355X-native module (HIP kernels, timm module tree and state_dict keys)
-for the backbones on the north-star path -- ConvNeXt-base/large and ConvNeXt V2-base/large
+for the backbones on the north-star path -- ConvNeXt-tiny/small/base/large and ConvNeXt V2-base/large
 (localization) and ResNet-18/50 (classification).  Every other name of the reference registry is
 recognised (``list_backbones`` returns the reference's full list) but raises: those families (and
-the other ConvNeXt V2 sizes) are outside this build's scope.
+ConvNeXt-xlarge and the other ConvNeXt V2 sizes) are outside this build's scope.
 ``pretrained=True`` cannot download weights offline; pass ``pretrained=False`` or load a timm
 state_dict with ``load_state_dict`` (keys match).
 """
@@ -53,8 +53,9 @@ _FAMILIES: dict[str, dict[str, str]] = {
 BACKBONES: dict[str, str] = {k: v for fam in _FAMILIES.values() for k, v in fam.items()}
 
 # names built natively on MI355X (the north-star backbones)
-NATIVE = ("convnext_base", "convnext_large", "convnextv2_base", "convnextv2_large", "resnet18", "resnet50")
-_FEATURE_DIMS = {"convnext_base": 1024, "convnext_large": 1536, "convnextv2_base": 1024, "convnextv2_large": 1536,
+NATIVE = ("convnext_tiny", "convnext_small", "convnext_base", "convnext_large", "convnextv2_base", "convnextv2_large",
+          "resnet18", "resnet50")
+_FEATURE_DIMS = {"convnext_tiny": 768, "convnext_small": 768, "convnext_base": 1024, "convnext_large": 1536, "convnextv2_base": 1024, "convnextv2_large": 1536,
                  "resnet18": 512, "resnet50": 2048}
 
 
