@@ -49,8 +49,6 @@ class GemmProbe:
 
 
 PROBES: list[GemmProbe] = []
-# single-probe alias kept for older tools (tools/*.py set K.PROBE)
-PROBE: GemmProbe | None = None
 
 
 class OpProbe:
@@ -190,8 +188,7 @@ def gemm(
     if fold is not None:  # (out, accumulate, counters): the split-K fold inside the GEMM (SV_EPI_SLAB)
         fo, facc, fcnt = fold
         d.fold_out, d.fold_ld, d.fold_accumulate, d.fold_counters = ptr(fo), N, int(bool(facc)), ptr(fcnt)
-    probes = [p_ for p_ in (PROBES + ([PROBE] if PROBE is not None else [])) if p_.matches(a_kmajor, b_kmajor,
-                                                                                      compute_bf16, epilogue)]
+    probes = [p_ for p_ in PROBES if p_.matches(a_kmajor, b_kmajor, compute_bf16, epilogue)]
     if probes:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
@@ -257,40 +254,47 @@ def linear_dgrad_ln(dh2d, w, z2d, mean, rstd, lnw, *, dw, db, policy=None):
         xch = _LN_XCH[key] = torch.empty(max(tilesM * tilesN * 512, 1 << 18), device=dh2d.device, dtype=torch.float32)
     bn = nv.BnRef(ptr(mean), ptr(rstd), ptr(lnw), None)
     try:
-        gemm(dh2d, w, M=M, N=C, K=K, a_kmajor=True, b_kmajor=False, lda=K, ldb=C, epilogue=nv.SV_EPI_LN_BWD, C=dz,
-             C2=part, aux=z2d, ld_aux=C, compute_bf16=True, bn=bn, policy=policy,
-             fold=(xch, False, _fold_counters(dh2d.device, tilesM)))
+        linear_dgrad(dh2d, w, out=dz, epilogue=nv.SV_EPI_LN_BWD, out2=part, aux=z2d, ld_aux=C, bn=bn, policy=policy,
+                     fold=(xch, False, _fold_counters(dh2d.device, tilesM)))
     except RuntimeError as err:
         if "(status 2)" in str(err):  # SV_ERR_UNSUPPORTED: not every tile resident at once (CU mask, grid cap)
             return None
         raise
-
-    def finish(record: bool = True, defer: list | None = None):
-        if record:
-            part.record_stream(torch.cuda.current_stream())
-        if defer is not None:
-            defer += [(part[0], dw, P, True), (part[1], db, P, True)]
-            return
-        reduce_pair(part[0], dw, part[1], db, P)
-
-    return dz, finish
+    return dz, _ln_partials_finish(part, P, dw, db)
 
 
+# The three operand layouts of the host paths; nothing else in this file names a layout (the conv paths and
+# linear_dgrad_ln pass their split / second output / BatchNorm / fold operands through these).
 def linear_fwd(x2d, w, *, out, bias=None, epilogue=nv.SV_EPI_STORE, out2=None, gamma=None, residual=None,
-               compute_bf16=True, policy=None):
+               compute_bf16=True, policy=None, split_k=1):
     """out[M,N] = epilogue(x2d[M,K] @ w[N,K]^T)  (torch Linear weight layout)."""
     M, K = x2d.shape
     N = w.shape[0]
     return gemm(x2d, w, M=M, N=N, K=K, a_kmajor=True, b_kmajor=True, lda=K, ldb=K, epilogue=epilogue, C=out,
-                C2=out2, bias=bias, gamma=gamma, aux=residual, compute_bf16=compute_bf16, policy=policy)
+                C2=out2, bias=bias, gamma=gamma, aux=residual, split_k=split_k, compute_bf16=compute_bf16,
+                policy=policy)
 
 
-def linear_dgrad(dy2d, w, *, out, epilogue=nv.SV_EPI_STORE, a_scale_k=None, aux=None, compute_bf16=True, policy=None):
+def linear_dgrad(dy2d, w, *, out, epilogue=nv.SV_EPI_STORE, a_scale_k=None, aux=None, compute_bf16=True, policy=None,
+                 split_k=1, out2=None, bn=None, gamma=None, ld_aux=None, fold=None):
     """out[M,K] = epilogue((dy2d[M,N] * a_scale_k[N]) @ w[N,K])."""
     M, N = dy2d.shape
     K = w.shape[1]
     return gemm(dy2d, w, M=M, N=K, K=N, a_kmajor=True, b_kmajor=False, lda=N, ldb=K, epilogue=epilogue, C=out,
-                a_scale_k=a_scale_k, aux=aux, compute_bf16=compute_bf16, policy=policy)
+                C2=out2, gamma=gamma, a_scale_k=a_scale_k, aux=aux, ld_aux=ld_aux, split_k=split_k,
+                compute_bf16=compute_bf16, bn=bn, policy=policy, fold=fold)
+
+
+def _wgrad_slabs(dy2d, x2d, K, split, *, bf16_slabs=False, cs=None, fold=None, compute_bf16=True, policy=None):
+    """The split-K slabs of G[N,K] = dy2d[M,N]^T x2d[M,:K] (SV_EPI_SLAB), f32 or -- ``bf16_slabs`` -- bf16;
+    ``cs``: receives the column sums of dy2d per slice; ``fold`` = (out, accumulate): the in-kernel fold's target."""
+    M, N = dy2d.shape
+    slab = torch.empty(split * N * K, device=dy2d.device, dtype=torch.bfloat16 if bf16_slabs else torch.float32)
+    if fold is not None:
+        fold = (*fold, _fold_counters(dy2d.device, -(-N // 256) * -(-K // 256)))
+    gemm(dy2d, x2d, M=N, N=K, K=M, a_kmajor=False, b_kmajor=False, lda=N, ldb=x2d.shape[1], epilogue=nv.SV_EPI_SLAB,
+         C=slab, C2=cs, split_k=split, compute_bf16=compute_bf16, policy=policy, fold=fold)
+    return slab
 
 
 # channel counts the fused MLP forward kernel (csrc/mlp.hip) is built for: ConvNeXt-base S1 / S2, ConvNeXt-large S1
@@ -454,57 +458,50 @@ def linear_wgrad(dy2d, x2d, *, out=None, accumulate=False, bias_out=None, bias_a
     first ``cols`` columns of x2d (the stem's 48 of its 64-wide padded patch rows).  ``defer`` (a list, with
     ``out`` given): append the slab folds to it for one ``reduce_multi`` launch instead of reducing here."""
     M, N = dy2d.shape
-    ldx = x2d.shape[1]
-    K = ldx if cols is None else cols
+    K = x2d.shape[1] if cols is None else cols
     split = _wgrad_split_for(N, K, M, wgrad_target)
     cs = torch.empty(split * N, device=dy2d.device, dtype=torch.float32) if bias_out is not None else None
-    if (out is not None and _bf16_slabs(N, K, M, split, compute_bf16, policy) and out.is_contiguous()
-            and out.numel() == N * K):
-        slab16 = torch.empty(split * N * K, device=dy2d.device, dtype=torch.bfloat16)
-        gemm(dy2d, x2d, M=N, N=K, K=M, a_kmajor=False, b_kmajor=False, lda=N, ldb=ldx, epilogue=nv.SV_EPI_SLAB,
-             C=slab16, C2=cs, split_k=split, compute_bf16=True, policy=policy)
-        _timed_call("fold", 2.0 * split * N * K + 4.0 * N * K * (1 + int(bool(accumulate))), "sv_reduce_partials_bf16",
-                    ptr(slab16), split, N * K, ptr(out), 1.0, int(bool(accumulate)))
-        if cs is not None:
-            if defer is not None:
-                defer.append((cs, bias_out, split, bias_accumulate))
-            else:
-                reduce_into(cs, split, bias_out, accumulate=bias_accumulate)
-        return out
-    slab = torch.empty(split * N * K, device=dy2d.device, dtype=torch.float32)
-    if out is not None and _fold_ok(split, N * K, out, compute_bf16):
+    # the form: bf16 slabs, else the in-kernel fold, else f32 slabs
+    bf16 = (out is not None and _bf16_slabs(N, K, M, split, compute_bf16, policy) and out.is_contiguous()
+            and out.numel() == N * K)
+    infold = not bf16 and out is not None and _fold_ok(split, N * K, out, compute_bf16)
+    if infold:
         _check(out.numel() == N * K, "linear_wgrad: bad out")
-        gemm(dy2d, x2d, M=N, N=K, K=M, a_kmajor=False, b_kmajor=False, lda=N, ldb=ldx, epilogue=nv.SV_EPI_SLAB,
-             C=slab, C2=cs, split_k=split, compute_bf16=compute_bf16, policy=policy,
-             fold=(out, accumulate, _fold_counters(dy2d.device, -(-N // 256) * -(-K // 256))))
-        if cs is not None:
-            if defer is not None:
-                defer.append((cs, bias_out, split, bias_accumulate))
-            else:
-                reduce_into(cs, split, bias_out, accumulate=bias_accumulate)
+    slab = _wgrad_slabs(dy2d, x2d, K, split, bf16_slabs=bf16, cs=cs, fold=(out, accumulate) if infold else None,
+                        compute_bf16=compute_bf16, policy=policy)
+    if bf16:
+        _timed_call("fold", 2.0 * split * N * K + 4.0 * N * K * (1 + int(bool(accumulate))), "sv_reduce_partials_bf16",
+                    ptr(slab), split, N * K, ptr(out), 1.0, int(bool(accumulate)))
+    if bf16 or infold:
+        _colsum_finish(cs, split, bias_out, bias_accumulate, defer)
         return out
-    gemm(dy2d, x2d, M=N, N=K, K=M, a_kmajor=False, b_kmajor=False, lda=N, ldb=ldx, epilogue=nv.SV_EPI_SLAB,
-         C=slab, C2=cs, split_k=split, compute_bf16=compute_bf16, policy=policy)
     if out is None:
         if split == 1 and not accumulate:
-            if cs is not None:
-                reduce_into(cs, split, bias_out, accumulate=bias_accumulate)
+            _colsum_finish(cs, split, bias_out, bias_accumulate, None)
             return slab.view(N, K)
         out = torch.empty(N, K, device=dy2d.device, dtype=torch.float32)
         accumulate = False
     _check(out.numel() == N * K and out.is_contiguous(), "linear_wgrad: bad out")
     if defer is not None:
         defer.append((slab, out, split, accumulate))
-        if cs is not None:
-            defer.append((cs, bias_out, split, bias_accumulate))
-        return out
-    if cs is not None and bias_accumulate == accumulate:
+        _colsum_finish(cs, split, bias_out, bias_accumulate, defer)
+    elif cs is not None and bias_accumulate == accumulate:
         reduce_pair(slab, out, cs, bias_out, split, accumulate=accumulate)
     else:
-        if cs is not None:
-            reduce_into(cs, split, bias_out, accumulate=bias_accumulate)
+        _colsum_finish(cs, split, bias_out, bias_accumulate, None)
         reduce_into(slab, split, out, accumulate)
     return out
+
+
+def _colsum_finish(cs, split, bias_out, accumulate, defer) -> None:
+    """The bias gradient from the wgrad GEMM's column-sum partials (none: nothing): folded here, or by the caller's
+    ``defer`` list."""
+    if cs is None:
+        return
+    if defer is not None:
+        defer.append((cs, bias_out, split, accumulate))
+    else:
+        reduce_into(cs, split, bias_out, accumulate=accumulate)
 
 
 def layerscale_wgrad(dsrc2d, a2d, w2, gamma, b2, *, dw2, dgamma, db2, compute_bf16=True, policy=None,
@@ -518,29 +515,22 @@ def layerscale_wgrad(dsrc2d, a2d, w2, gamma, b2, *, dw2, dgamma, db2, compute_bf
     K4 = a2d.shape[1]
     split = _wgrad_split_for(C, K4, M, wgrad_target)
     cs = torch.empty(split * C, device=dsrc2d.device, dtype=torch.float32)
-    if _bf16_slabs(C, K4, M, split, compute_bf16, policy):
-        slab16 = torch.empty(split * C * K4, device=dsrc2d.device, dtype=torch.bfloat16)
-        gemm(dsrc2d, a2d, M=C, N=K4, K=M, a_kmajor=False, b_kmajor=False, lda=C, ldb=K4, epilogue=nv.SV_EPI_SLAB,
-             C=slab16, C2=cs, split_k=split, compute_bf16=True, policy=policy)
+    bf16 = _bf16_slabs(C, K4, M, split, compute_bf16, policy)
+    # G = d^T a folded inside the wgrad GEMM (opt-in); the finish then reads one G instead of `split` slabs
+    G = None if bf16 else torch.empty(C * K4, device=dsrc2d.device, dtype=torch.float32)
+    infold = not bf16 and _fold_ok(split, C * K4, G, compute_bf16)
+    slab = _wgrad_slabs(dsrc2d, a2d, K4, split, bf16_slabs=bf16, cs=cs, fold=(G, False) if infold else None,
+                        compute_bf16=compute_bf16, policy=policy)
+    rest = (ptr(cs), split, ptr(w2), ptr(gamma), ptr(b2), ptr(dw2), ptr(dgamma), ptr(db2))
+    if bf16:
         _timed_call("fold", 2.0 * split * C * K4 + 8.0 * C * K4 + 4.0 * (split + 4) * C,
-                    "sv_layerscale_wgrad_reduce_bf16", ptr(slab16), ptr(cs), split, ptr(w2), ptr(gamma), ptr(b2),
-                    ptr(dw2), ptr(dgamma), ptr(db2), C, K4)
-        return
-    slab = torch.empty(split * C * K4, device=dsrc2d.device, dtype=torch.float32)
-    G = torch.empty(C * K4, device=dsrc2d.device, dtype=torch.float32)
-    if _fold_ok(split, C * K4, G, compute_bf16):
-        # G = d^T a folded inside the wgrad GEMM; the finish then reads one G instead of `split` slabs
-        gemm(dsrc2d, a2d, M=C, N=K4, K=M, a_kmajor=False, b_kmajor=False, lda=C, ldb=K4, epilogue=nv.SV_EPI_SLAB,
-             C=slab, C2=cs, split_k=split, compute_bf16=compute_bf16, policy=policy,
-             fold=(G, False, _fold_counters(dsrc2d.device, -(-C // 256) * -(-K4 // 256))))
-        _timed_call("fold", 4.0 * (3 * C * K4 + (split + 4) * C), "sv_layerscale_wgrad_fold_finish", ptr(G), ptr(cs),
-                    split, ptr(w2), ptr(gamma), ptr(b2), ptr(dw2), ptr(dgamma), ptr(db2), C, K4)
-        return
-    gemm(dsrc2d, a2d, M=C, N=K4, K=M, a_kmajor=False, b_kmajor=False, lda=C, ldb=K4, epilogue=nv.SV_EPI_SLAB,
-         C=slab, C2=cs, split_k=split, compute_bf16=compute_bf16, policy=policy)
-    _timed_call("fold", 4.0 * ((split + 2) * C * K4 + (split + 4) * C),
-                "sv_layerscale_wgrad_reduce", ptr(slab), ptr(cs), split, ptr(w2), ptr(gamma), ptr(b2), ptr(dw2),
-                ptr(dgamma), ptr(db2), None, C, K4)
+                    "sv_layerscale_wgrad_reduce_bf16", ptr(slab), *rest, C, K4)
+    elif infold:
+        _timed_call("fold", 4.0 * (3 * C * K4 + (split + 4) * C), "sv_layerscale_wgrad_fold_finish", ptr(G), *rest,
+                    C, K4)
+    else:
+        _timed_call("fold", 4.0 * ((split + 2) * C * K4 + (split + 4) * C), "sv_layerscale_wgrad_reduce", ptr(slab),
+                    *rest, None, C, K4)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -580,6 +570,19 @@ def reduce_multi(segs: list, alpha: float = 1.0) -> None:
             arr[j] = nv.RedSeg(ptr(part), ptr(out), n, int(P), int(bool(acc)))
             moved += 4.0 * n * (P + 1 + int(bool(acc)))
         _timed_call("fold", moved, "sv_reduce_partials_multi", arr, len(chunk), float(alpha))
+
+
+def _ln_partials_finish(part: torch.Tensor, P: int, dw: torch.Tensor, db: torch.Tensor):
+    """finish(record, defer) of a LayerNorm backward's weight / bias partials ``part`` [2][P * C]: folds them into
+    dw / db on whatever stream is current when it is called (layernorm_bwd(defer_reduce=True), linear_dgrad_ln)."""
+    def finish(record: bool = True, defer: list | None = None):
+        if record:  # the caller may instead keep the partials alive until the streams have joined
+            part.record_stream(torch.cuda.current_stream())
+        if defer is not None:  # folded by the caller's reduce_multi launch
+            defer += [(part[0], dw, P, True), (part[1], db, P, True)]
+            return
+        reduce_pair(part[0], dw, part[1], db, P)
+    return finish
 
 
 def colsum_into(x2d: torch.Tensor, out: torch.Tensor, accumulate: bool = True):
@@ -624,14 +627,7 @@ def layernorm_bwd(dy2d, x2d, mean, rstd, w, *, dw, db, dx=None, accumulate_dx=Fa
     _timed_call("ln_bwd", nb, "sv_layernorm_bwd", ptr(dy2d), dt(dy2d), ptr(x2d), dt(x2d), ptr(mean), ptr(rstd), ptr(w),
                 ptr(dx), dt(dx), int(accumulate_dx), ptr(pw[0]), ptr(pw[1]), rows, C)
     if defer_reduce:
-        def finish(record: bool = True, defer: list | None = None):
-            if record:  # the caller may instead keep pw alive until the streams have joined
-                pw.record_stream(torch.cuda.current_stream())
-            if defer is not None:  # folded by the caller's reduce_multi launch
-                defer += [(pw[0], dw, P, True), (pw[1], db, P, True)]
-                return
-            reduce_pair(pw[0], dw, pw[1], db, P)
-        return dx, finish
+        return dx, _ln_partials_finish(pw, P, dw, db)
     if dw is not None and db is not None:
         reduce_pair(pw[0], dw, pw[1], db, P)
     elif dw is not None:
@@ -1189,18 +1185,15 @@ def _slab_finish(work: torch.Tensor, split: int, M: int, N: int, C: torch.Tensor
 def _pointwise_fwd(x, wp, s, y, M, stats=None, policy=None):
     """1x1 conv forward as a GEMM over [M, Cs] rows; split-K + slab finish when the grid is small."""
     split = _conv_split(M, s.Cout, s.Cs)
+    x2d, w2d = x.view(M, s.Cs), wp.view(s.Cout, s.Cs)
     if split > 1:
         work = torch.empty(split * M * s.Cout, device=x.device, dtype=torch.float32)
-        gemm(x.view(M, s.Cs), wp.view(s.Cout, s.Cs), M=M, N=s.Cout, K=s.Cs, a_kmajor=True, b_kmajor=True, lda=s.Cs,
-             ldb=s.Cs, C=work, epilogue=nv.SV_EPI_SLAB, split_k=split, compute_bf16=True, policy=policy)
+        linear_fwd(x2d, w2d, out=work, epilogue=nv.SV_EPI_SLAB, split_k=split, policy=policy)
         _slab_finish(work, split, M, s.Cout, y, stats=stats)
     elif stats is not None:
-        gemm(x.view(M, s.Cs), wp.view(s.Cout, s.Cs), M=M, N=s.Cout, K=s.Cs, a_kmajor=True, b_kmajor=True, lda=s.Cs,
-             ldb=s.Cs, C=y.view(M, s.Cout), C2=stats, epilogue=nv.SV_EPI_STORE_STATS, compute_bf16=True,
-             policy=policy)
+        linear_fwd(x2d, w2d, out=y.view(M, s.Cout), out2=stats, epilogue=nv.SV_EPI_STORE_STATS, policy=policy)
     else:
-        gemm(x.view(M, s.Cs), wp.view(s.Cout, s.Cs), M=M, N=s.Cout, K=s.Cs, a_kmajor=True, b_kmajor=True, lda=s.Cs,
-             ldb=s.Cs, C=y.view(M, s.Cout), compute_bf16=True, policy=policy)
+        linear_fwd(x2d, w2d, out=y.view(M, s.Cout), policy=policy)
 
 
 def conv_fwd(x: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, out_dtype: torch.dtype,
@@ -1294,19 +1287,16 @@ def conv_bwd_data(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, *, dx: to
     if _pointwise(s, wp.dtype) and (not accumulate or dx.dtype == torch.float32):
         M = s.B * s.H * s.W
         split = _conv_split(M, s.Cs, s.Cout)
+        dy2d, w2d = dy.view(M, s.Cout), wp.view(s.Cout, s.Cs)
         if split > 1:
             work = torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32)
-            gemm(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), M=M, N=s.Cs, K=s.Cout, a_kmajor=True, b_kmajor=False,
-                 lda=s.Cout, ldb=s.Cs, C=work, epilogue=nv.SV_EPI_SLAB, split_k=split, compute_bf16=True, policy=policy)
+            linear_dgrad(dy2d, w2d, out=work, epilogue=nv.SV_EPI_SLAB, split_k=split, policy=policy)
             _slab_finish(work, split, M, s.Cs, dx, accumulate=accumulate)
         elif accumulate:  # dx += dy W: the layer-scale/residual epilogue with gamma = 1, residual = dx (in place)
-            ones = _ones(s.Cs, dy.device)
-            gemm(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), M=M, N=s.Cs, K=s.Cout, a_kmajor=True, b_kmajor=False,
-                 lda=s.Cout, ldb=s.Cs, C=dx.view(M, s.Cs), epilogue=nv.SV_EPI_BIAS_GAMMA_RES, gamma=ones,
-                 aux=dx.view(M, s.Cs), compute_bf16=True, policy=policy)
+            linear_dgrad(dy2d, w2d, out=dx.view(M, s.Cs), epilogue=nv.SV_EPI_BIAS_GAMMA_RES,
+                         gamma=_ones(s.Cs, dy.device), aux=dx.view(M, s.Cs), policy=policy)
         else:
-            gemm(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), M=M, N=s.Cs, K=s.Cout, a_kmajor=True, b_kmajor=False,
-                 lda=s.Cout, ldb=s.Cs, C=dx.view(M, s.Cs), compute_bf16=True, policy=policy)
+            linear_dgrad(dy2d, w2d, out=dx.view(M, s.Cs), policy=policy)
         return dx
     T = s.KH * s.KW
     # (a bf16 dx accumulates here too -- the ResNet gradient stream: the sum in f32, stored bf16 -- rather than in
@@ -1405,13 +1395,12 @@ def conv_bwd_data_bn(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, y: tor
     part = torch.empty(prows, 2, s.Cs, device=dy.device, dtype=torch.float32)
     work = torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32) if split > 1 else None
     if pw and split > 1:
-        gemm(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), M=M, N=s.Cs, K=s.Cout, a_kmajor=True, b_kmajor=False,
-             lda=s.Cout, ldb=s.Cs, C=work, epilogue=nv.SV_EPI_SLAB, split_k=split, compute_bf16=True, policy=policy)
+        linear_dgrad(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), out=work, epilogue=nv.SV_EPI_SLAB, split_k=split,
+                     policy=policy)
         call("sv_gemm_slab_finish_bn_bwd", ptr(work), split, M, s.Cs, ptr(dx), ptr(y), ctypes.byref(ref), ptr(part))
     elif pw:
-        gemm(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), M=M, N=s.Cs, K=s.Cout, a_kmajor=True, b_kmajor=False,
-             lda=s.Cout, ldb=s.Cs, C=dx.view(M, s.Cs), C2=part, epilogue=nv.SV_EPI_STORE_BN_BWD,
-             aux=y.view(M, s.Cs), compute_bf16=True, bn=ref, policy=policy)
+        linear_dgrad(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), out=dx.view(M, s.Cs), out2=part,
+                     epilogue=nv.SV_EPI_STORE_BN_BWD, aux=y.view(M, s.Cs), bn=ref, policy=policy)
     else:
         call("sv_conv_bwd_data_bn", ptr(dy), ptr(wp), ptr(dx), dt(wp), ctypes.byref(s), ptr(y), ctypes.byref(ref),
              ptr(part), ptr(work), split, nv.pol_ref(policy))
@@ -1567,11 +1556,9 @@ def bn_fold_timeouts(device) -> int:
     return sum(int(ctl[3].item()) for (d, _), (ctl, _) in _FOLD_WS.items() if d == device)
 
 
-def bn_act_fold(y2d, part, bn_params: tuple, *, res=None, res_part=None, res_params: tuple | None = None,
-                relu=True, out_dtype=torch.float32):
-    """bn_act_small's contract at any row count the fold kernels take (bn_fold_ok): the statistics fold of the conv
-    epilogue's partials inside the activation pass (sv_bn_act_fold) -- bit for bit ``bn_stats_from_partials`` +
-    ``bn_act``.  -> (out, mean, rstd[, mean2, rstd2])."""
+def _bn_act_args(y2d, part, bn_params, res, res_part, res_params, relu, out_dtype) -> tuple:
+    """The outputs and the marshalled arguments that sv_bn_act_small and sv_bn_act_fold share (the fold appends its
+    workspace) -> (args, (out, mean, rstd[, mean2, rstd2])); without ``res_part`` the shortcut's operands are NULL / 0."""
     rows, C = y2d.shape
     g, b, eps, mom, rm, rv, nbt = bn_params
     dev = y2d.device
@@ -1584,14 +1571,21 @@ def bn_act_fold(y2d, part, bn_params: tuple, *, res=None, res_part=None, res_par
     else:
         g2 = b2 = rm2 = rv2 = nbt2 = mean2 = rstd2 = None
         eps2, mom2 = 0.0, 0.0
-    ctl, ws = _fold_ws(dev)
-    _fin("sv_bn_act_fold", ptr(y2d), dt(y2d), ptr(part), part.shape[0], float(eps), float(mom), ptr(g), ptr(b),
-         ptr(mean), ptr(rstd), ptr(rm), ptr(rv), ptr(nbt), ptr(res), nv.dt_none(res), ptr(res_part),
-         res_part.shape[0] if res_part is not None else 0, float(eps2), float(mom2), ptr(g2), ptr(b2), ptr(mean2),
-         ptr(rstd2), ptr(rm2), ptr(rv2), ptr(nbt2), int(relu), ptr(out), dt(out), rows, C, ptr(ctl), ptr(ws))
-    if res_part is not None:
-        return out, mean, rstd, mean2, rstd2
-    return out, mean, rstd
+    args = (ptr(y2d), dt(y2d), ptr(part), part.shape[0], float(eps), float(mom), ptr(g), ptr(b), ptr(mean), ptr(rstd),
+            ptr(rm), ptr(rv), ptr(nbt), ptr(res), nv.dt_none(res), ptr(res_part),
+            res_part.shape[0] if res_part is not None else 0, float(eps2), float(mom2), ptr(g2), ptr(b2), ptr(mean2),
+            ptr(rstd2), ptr(rm2), ptr(rv2), ptr(nbt2), int(relu), ptr(out), dt(out), rows, C)
+    return args, ((out, mean, rstd, mean2, rstd2) if res_part is not None else (out, mean, rstd))
+
+
+def bn_act_fold(y2d, part, bn_params: tuple, *, res=None, res_part=None, res_params: tuple | None = None,
+                relu=True, out_dtype=torch.float32):
+    """bn_act_small's contract at any row count the fold kernels take (bn_fold_ok): the statistics fold of the conv
+    epilogue's partials inside the activation pass (sv_bn_act_fold) -- bit for bit ``bn_stats_from_partials`` +
+    ``bn_act``.  -> (out, mean, rstd[, mean2, rstd2])."""
+    args, ret = _bn_act_args(y2d, part, bn_params, res, res_part, res_params, relu, out_dtype)
+    _fin("sv_bn_act_fold", *args, *_fin_ws(y2d.device))
+    return ret
 
 
 def bn_act_partials(y2d, part, bn_params: tuple, *, res=None, res_part=None, res_params: tuple | None = None,
@@ -1629,25 +1623,52 @@ def bn_act_small(y2d, part, bn_params: tuple, *, res=None, res_part=None, res_pa
     ONE launch (sv_bn_act_small): bit for bit ``bn_stats_from_partials`` + ``bn_act``.  ``bn_params`` =
     (gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked); with ``res_part`` the residual is
     the projection shortcut's conv output and ``res_params`` its BatchNorm's.  -> (out, mean, rstd[, mean2, rstd2])."""
-    rows, C = y2d.shape
-    g, b, eps, mom, rm, rv, nbt = bn_params
-    dev = y2d.device
-    mean = torch.empty(C, device=dev, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
-    out = torch.empty(rows, C, device=dev, dtype=out_dtype)
-    if res_part is not None:
-        g2, b2, eps2, mom2, rm2, rv2, nbt2 = res_params
-        mean2, rstd2 = torch.empty_like(mean), torch.empty_like(mean)
-    else:
-        g2 = b2 = rm2 = rv2 = nbt2 = mean2 = rstd2 = None
-        eps2, mom2 = 0.0, 0.0
-    call("sv_bn_act_small", ptr(y2d), dt(y2d), ptr(part), part.shape[0], float(eps), float(mom), ptr(g), ptr(b),
-         ptr(mean), ptr(rstd), ptr(rm), ptr(rv), ptr(nbt), ptr(res), nv.dt_none(res), ptr(res_part),
-         res_part.shape[0] if res_part is not None else 0, float(eps2), float(mom2), ptr(g2), ptr(b2), ptr(mean2),
-         ptr(rstd2), ptr(rm2), ptr(rv2), ptr(nbt2), int(relu), ptr(out), dt(out), rows, C)
-    if res_part is not None:
-        return out, mean, rstd, mean2, rstd2
-    return out, mean, rstd
+    args, ret = _bn_act_args(y2d, part, bn_params, res, res_part, res_params, relu, out_dtype)
+    call("sv_bn_act_small", *args)
+    return ret
+
+
+# The two wide BatchNorm backward entry points, marshalled once each: operands a call site does not name are NULL / 0.
+# ``y2 / mean2 / rstd2 / gamma2`` (the DUAL mode's second BatchNorm) make the result (dx, dx2).
+def _bn_bwd_small(mode, dout, y, mean, rstd, gamma, *, dx_dtype, batch_stats, act=None, beta=None, y2=None, mean2=None,
+                  rstd2=None, gamma2=None, part=None, dgamma=None, dbeta=None, dgamma2=None, dbeta2=None):
+    """The whole BatchNorm backward in one launch (sv_bn_bwd_small); ``part``: statistics partials already summed."""
+    rows, C = y.shape
+    dx = torch.empty(rows, C, device=y.device, dtype=dx_dtype)
+    dx2 = torch.empty_like(dx) if y2 is not None else None
+    call("sv_bn_bwd_small", mode, ptr(dout), dt(dout), ptr(act), nv.dt_none(act), ptr(y), dt(y), ptr(mean), ptr(rstd),
+         ptr(gamma), ptr(beta), ptr(y2), dt(y2) if y2 is not None else 0, ptr(mean2), ptr(rstd2), ptr(gamma2),
+         ptr(part), part.shape[0] if part is not None else 0, ptr(dx), ptr(dx2), dt(dx), ptr(dgamma), ptr(dbeta),
+         ptr(dgamma2), ptr(dbeta2), int(batch_stats), rows, C)
+    return dx if y2 is None else (dx, dx2)
+
+
+def _bn_bwd_apply_fold(mode, dout, y, mean, rstd, gamma, part, P, *, dx_dtype, batch_stats, idx=None, H=0, W=0,
+                       beta=None, y2=None, mean2=None, rstd2=None, gamma2=None, part2=None, dgamma=None, dbeta=None,
+                       dgamma2=None, dbeta2=None):
+    """The statistics finish inside the apply pass (sv_bn_bwd_apply_fold); ``idx / H / W``: dout is a max-pool's
+    output gradient, gathered through the pool's indices."""
+    rows, C = y.shape
+    dx = torch.empty(rows, C, device=y.device, dtype=dx_dtype)
+    dx2 = torch.empty_like(dx) if y2 is not None else None
+    _fin("sv_bn_bwd_apply_fold", mode, ptr(dout), dt(dout), ptr(idx), H, W, ptr(y), dt(y), ptr(mean), ptr(rstd),
+         ptr(gamma), ptr(beta), ptr(y2), dt(y2) if y2 is not None else 0, ptr(mean2), ptr(rstd2), ptr(gamma2),
+         ptr(part), ptr(part2), P, ptr(dx), ptr(dx2), dt(dx), ptr(dgamma), ptr(dbeta), ptr(dgamma2), ptr(dbeta2),
+         int(batch_stats), rows, C, *_fin_ws(y.device))
+    return dx if y2 is None else (dx, dx2)
+
+
+def _bn_bwd_sums(P: int, C: int, batch_stats: bool, *folds) -> torch.Tensor:
+    """The separate finish: one sv_bn_bwd_finish per (part, dgamma, dbeta) of ``folds`` into ONE buffer -> sums
+    [len(folds)][2][C] for the apply pass (dgamma / dbeta accumulate); eval mode zeroes it with one launch."""
+    dev = folds[0][0].device
+    sums = torch.empty(len(folds), 2, C, device=dev, dtype=torch.float32)
+    ws = _fin_ws(dev)
+    for i, (part, dgamma, dbeta) in enumerate(folds):  # into sums[i] (2 * C floats each), without a view per fold
+        _fin("sv_bn_bwd_finish", ptr(part), P, C, ptr(sums) + i * 8 * C, ptr(dgamma), ptr(dbeta), *ws)
+    if not batch_stats:
+        sums.zero_()
+    return sums
 
 
 def bn_bwd(dout2d, y2d, mean, rstd, gamma, *, act=None, relu_beta=None, dgamma=None, dbeta=None,
@@ -1675,50 +1696,36 @@ def bn_bwd(dout2d, y2d, mean, rstd, gamma, *, act=None, relu_beta=None, dgamma=N
     if mask_inplace:
         _check(act is not None and gmask is None and dout2d.dtype in (torch.float32, torch.bfloat16),
                "bn_bwd: mask_inplace needs act, an f32 / bf16 dout and no gmask")
-    given = part is not None
-    if given:
+    if part is not None:
         _check(relu_beta is not None and part.dtype == torch.float32 and part.is_contiguous() and part.dim() == 3
                and tuple(part.shape[1:]) == (2, C), "bn_bwd: part must be f32 [P][2][C] (relu_beta form)")
     small_mode = (nv.SV_BN_SMALL_RELU if relu_beta is not None else nv.SV_BN_SMALL_MASK if mask_inplace else None)
     if (small_mode is not None and gmask is None and bn_small_ok(rows, C)
             and _bn_small_args_ok(dout2d, y2d, mean, rstd, gamma, act, relu_beta, part, dgamma, dbeta)):
-        dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-        call("sv_bn_bwd_small", small_mode, ptr(dout2d), dt(dout2d), ptr(act), nv.dt_none(act), ptr(y2d), dt(y2d),
-             ptr(mean), ptr(rstd), ptr(gamma), ptr(relu_beta), None, 0, None, None, None, ptr(part),
-             part.shape[0] if given else 0, ptr(dx), None, dt(dx), ptr(dgamma), ptr(dbeta), None, None,
-             int(batch_stats), rows, C)
-        return dx
-    if given:
+        return _bn_bwd_small(small_mode, dout2d, y2d, mean, rstd, gamma, act=act, beta=relu_beta, part=part,
+                             dgamma=dgamma, dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats)
+    if part is not None:  # summed by dout's producer (conv_bwd_data_bn)
         P = part.shape[0]
     else:
         P = value("sv_bn_nparts", rows, C)
         part = torch.empty(P, 2, C, device=y2d.device, dtype=torch.float32)
-    if given:
-        pass  # summed by dout's producer (conv_bwd_data_bn)
-    elif relu_beta is not None:
-        call("sv_bn_relu_bwd_stats", ptr(dout2d), dt(dout2d), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma),
-             ptr(relu_beta), rows, C, ptr(part))
-    elif mask_inplace:
-        call("sv_bn_bwd_stats_mask", ptr(dout2d), dt(dout2d), ptr(act), dt(act), ptr(y2d), dt(y2d), ptr(mean),
-             ptr(rstd), rows, C, ptr(part))
-        act = None  # dout now holds the masked gradient
-    else:
-        call("sv_bn_bwd_stats", ptr(dout2d), dt(dout2d), ptr(act), nv.dt_none(act), ptr(y2d), dt(y2d), ptr(mean),
-             ptr(rstd), rows, C, ptr(part))
+        if relu_beta is not None:
+            call("sv_bn_relu_bwd_stats", ptr(dout2d), dt(dout2d), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma),
+                 ptr(relu_beta), rows, C, ptr(part))
+        elif mask_inplace:
+            call("sv_bn_bwd_stats_mask", ptr(dout2d), dt(dout2d), ptr(act), dt(act), ptr(y2d), dt(y2d), ptr(mean),
+                 ptr(rstd), rows, C, ptr(part))
+            act = None  # dout now holds the masked gradient
+        else:
+            call("sv_bn_bwd_stats", ptr(dout2d), dt(dout2d), ptr(act), nv.dt_none(act), ptr(y2d), dt(y2d), ptr(mean),
+                 ptr(rstd), rows, C, ptr(part))
     if ((relu_beta is not None or act is None) and gmask is None and bn_fold_ok(rows, C, P)
             and _bn_small_args_ok(dout2d, y2d, mean, rstd, gamma, relu_beta, part)):
-        # the finish inside the apply pass (sv_bn_bwd_apply_fold): MASK = dout already masked (mask_inplace)
-        dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-        ctl, ws = _fold_ws(y2d.device)
+        # MASK = dout already masked (mask_inplace)
         mode = nv.SV_BN_SMALL_RELU if relu_beta is not None else nv.SV_BN_SMALL_MASK
-        _fin("sv_bn_bwd_apply_fold", mode, ptr(dout2d), dt(dout2d), None, 0, 0, ptr(y2d), dt(y2d), ptr(mean),
-             ptr(rstd), ptr(gamma), ptr(relu_beta), None, 0, None, None, None, ptr(part), None, P, ptr(dx), None,
-             dt(dx), ptr(dgamma), ptr(dbeta), None, None, int(batch_stats), rows, C, ptr(ctl), ptr(ws))
-        return dx
-    sums = torch.empty(2, C, device=y2d.device, dtype=torch.float32)
-    _fin("sv_bn_bwd_finish", ptr(part), P, C, ptr(sums), ptr(dgamma), ptr(dbeta), *_fin_ws(part.device))
-    if not batch_stats:
-        sums.zero_()
+        return _bn_bwd_apply_fold(mode, dout2d, y2d, mean, rstd, gamma, part, P, beta=relu_beta, dgamma=dgamma,
+                                  dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats)
+    sums = _bn_bwd_sums(P, C, batch_stats, (part, dgamma, dbeta))
     dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
     if relu_beta is not None:
         call("sv_bn_relu_bwd_apply", ptr(dout2d), dt(dout2d), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma),
@@ -1739,32 +1746,18 @@ def bn_bwd_dual(gm, y2d, mean, rstd, gamma, act, y2, mean2, rstd2, gamma2, *, dg
     _check(_bn_c_ok(C) and gm.dtype in (torch.float32, torch.bfloat16) and gm.numel() == rows * C and gm.is_contiguous()
            and act.numel() == rows * C and act.is_contiguous() and y2.numel() == rows * C and y2.is_contiguous(),
            "bn_bwd_dual: bad shapes")
+    both = dict(y2=y2, mean2=mean2, rstd2=rstd2, gamma2=gamma2, dgamma=dgamma, dbeta=dbeta, dgamma2=dgamma2,
+                dbeta2=dbeta2, dx_dtype=dx_dtype, batch_stats=batch_stats)
     if bn_small_ok(rows, C) and _bn_small_args_ok(gm, y2d, mean, rstd, gamma, act, y2, mean2, rstd2, gamma2, dgamma,
                                                    dbeta, dgamma2, dbeta2):
-        dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-        dx2 = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-        call("sv_bn_bwd_small", nv.SV_BN_SMALL_DUAL, ptr(gm), dt(gm), ptr(act), dt(act), ptr(y2d), dt(y2d), ptr(mean),
-             ptr(rstd), ptr(gamma), None, ptr(y2), dt(y2), ptr(mean2), ptr(rstd2), ptr(gamma2), None, 0, ptr(dx),
-             ptr(dx2), dt(dx), ptr(dgamma), ptr(dbeta), ptr(dgamma2), ptr(dbeta2), int(batch_stats), rows, C)
-        return dx, dx2
+        return _bn_bwd_small(nv.SV_BN_SMALL_DUAL, gm, y2d, mean, rstd, gamma, act=act, **both)
     P = value("sv_bn_nparts", rows, C)
     part = torch.empty(2, P, 2, C, device=y2d.device, dtype=torch.float32)
     call("sv_bn_bwd_stats_mask_dual", ptr(gm), dt(gm), ptr(act), dt(act), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd),
          ptr(y2), dt(y2), ptr(mean2), ptr(rstd2), rows, C, ptr(part[0]), ptr(part[1]))
     if bn_fold_ok(rows, C, P) and _bn_small_args_ok(gm, y2d, mean, rstd, gamma, y2, mean2, rstd2, gamma2):
-        dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-        dx2 = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-        ctl, ws = _fold_ws(y2d.device)
-        _fin("sv_bn_bwd_apply_fold", nv.SV_BN_SMALL_DUAL, ptr(gm), dt(gm), None, 0, 0, ptr(y2d), dt(y2d), ptr(mean),
-             ptr(rstd), ptr(gamma), None, ptr(y2), dt(y2), ptr(mean2), ptr(rstd2), ptr(gamma2), ptr(part[0]),
-             ptr(part[1]), P, ptr(dx), ptr(dx2), dt(dx), ptr(dgamma), ptr(dbeta), ptr(dgamma2), ptr(dbeta2),
-             int(batch_stats), rows, C, ptr(ctl), ptr(ws))
-        return dx, dx2
-    sums = torch.empty(2, 2, C, device=y2d.device, dtype=torch.float32)
-    _fin("sv_bn_bwd_finish", ptr(part[0]), P, C, ptr(sums[0]), ptr(dgamma), ptr(dbeta), *_fin_ws(part.device))
-    _fin("sv_bn_bwd_finish", ptr(part[1]), P, C, ptr(sums[1]), ptr(dgamma2), ptr(dbeta2), *_fin_ws(part.device))
-    if not batch_stats:
-        sums.zero_()
+        return _bn_bwd_apply_fold(nv.SV_BN_SMALL_DUAL, gm, y2d, mean, rstd, gamma, part[0], P, part2=part[1], **both)
+    sums = _bn_bwd_sums(P, C, batch_stats, (part[0], dgamma, dbeta), (part[1], dgamma2, dbeta2))
     dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
     dx2 = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
     call("sv_bn_bwd_apply_dual", ptr(gm), dt(gm), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma), ptr(sums[0]),
@@ -1787,16 +1780,9 @@ def bn_relu_bwd_pooled(dpool4d: torch.Tensor, idx: torch.Tensor, H: int, W: int,
          ptr(rstd), ptr(gamma), ptr(beta), C, ptr(part))
     if (bn_fold_ok(rows, C, P) and rows * C < 2 ** 31
             and _bn_small_args_ok(dpool4d, y2d, mean, rstd, gamma, beta)):
-        dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-        ctl, ws = _fold_ws(y2d.device)
-        _fin("sv_bn_bwd_apply_fold", nv.SV_BN_SMALL_RELU, ptr(dpool4d), dt(dpool4d), ptr(idx), H, W, ptr(y2d), dt(y2d),
-             ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), None, 0, None, None, None, ptr(part), None, P, ptr(dx),
-             None, dt(dx), ptr(dgamma), ptr(dbeta), None, None, int(batch_stats), rows, C, ptr(ctl), ptr(ws))
-        return dx
-    sums = torch.empty(2, C, device=y2d.device, dtype=torch.float32)
-    _fin("sv_bn_bwd_finish", ptr(part), P, C, ptr(sums), ptr(dgamma), ptr(dbeta), *_fin_ws(part.device))
-    if not batch_stats:
-        sums.zero_()
+        return _bn_bwd_apply_fold(nv.SV_BN_SMALL_RELU, dpool4d, y2d, mean, rstd, gamma, part, P, idx=idx, H=H, W=W,
+                                  beta=beta, dgamma=dgamma, dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats)
+    sums = _bn_bwd_sums(P, C, batch_stats, (part, dgamma, dbeta))
     dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
     call("sv_bn_relu_bwd_apply_pool", ptr(dpool4d), dt(dpool4d), ptr(idx), B, H, W, ptr(y2d), dt(y2d), ptr(mean),
          ptr(rstd), ptr(gamma), ptr(beta), ptr(sums), ptr(dx), dt(dx), C)

@@ -149,6 +149,21 @@ def test_wgrad_split_and_bias(dev, M, compute_bf16, slabs, monkeypatch):
     assert rel(bias, q(dy).sum(0) + 1) < (2e-3 if compute_bf16 else 1e-5)
 
 
+def test_wgrad_unsplit_returns_the_slab(dev):
+    """``out=None`` with one K slice (the 256x128 family): the GEMM's only f32 slab comes back as G, and the bias
+    column sums still accumulate into ``bias_out``."""
+    M, N, Kd = 100, 64, 96
+    assert K._wgrad_split_for(N, Kd, M) == 1
+    g = torch.Generator().manual_seed(3)
+    dy = torch.randn(M, N, generator=g).to(torch.bfloat16)
+    x = torch.randn(M, Kd, generator=g).to(torch.bfloat16)
+    bias = torch.ones(N, device=dev)
+    G = K.linear_wgrad(dy.to(dev), x.to(dev), bias_out=bias)
+    assert tuple(G.shape) == (N, Kd) and G.dtype == torch.float32
+    assert rel(G, dy.double().t() @ x.double()) < 2e-3
+    assert rel(bias, dy.double().sum(0) + 1) < 2e-3
+
+
 def test_reduce_partials_deep(dev):
     g = torch.Generator().manual_seed(3)
     P, n = 300, 12345 * 4
