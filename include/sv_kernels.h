@@ -572,6 +572,44 @@ int sv_conv_bwd_data_split(const void* dy, const void* wp, void* dx, int32_t dx_
 int sv_conv_bwd_data_bn(const void* dy, const void* wp, void* dx, int32_t dtype, const sv_conv_shape* s,
                         const void* y, const sv_bn_ref* bn, float* part, float* work, int32_t split,
                         const sv_gemm_policy* policy, sv_stream_t stream);
+/* ---- grouped 3x3 convolution (csrc/gconv.hip) --------------------------------------------------
+ * Replaces timm Bottleneck.conv2 with cardinality > 1 (ResNeXt: Conv2d(width, width, 3, stride, padding=1,
+ * groups=32, bias=False), timm/models/resnet.py, built at spine_vision/training/models/backbone.py:166 for
+ * "resnext50") and its autograd data / weight gradients.  NHWC bf16 activations, f32 accumulation on MFMA:
+ *   x  [B][H][W][C],  y / dy [B][OH][OW][C],  OH = (H - 1) / stride + 1,  w torch [C][C/groups][3][3] f32.
+ * Supported: 3x3, pad 1, stride 1 or 2, C % 32 == 0, C / groups in {4, 8, 16, 32}; anything else returns
+ * SV_ERR_UNSUPPORTED before any launch.  Every device pointer 16-byte aligned.
+ *   sv_gconv_weight_pack  up to SV_MAX_GPACK_SEGS weights in one launch: for each, the forward form wp_fwd and the
+ *                         backward-data form wp_bwd (taps flipped, every group's block transposed), each
+ *                         [C/32][9][2][64][8] bf16 = 288 C elements: per block of 32 channels and tap the 32 x 32
+ *                         block-diagonal matrix (zeros across groups) as the MFMA A fragments the kernels load.
+ *   sv_gconv_fwd          y = conv(x, w)                         (wp_fwd)
+ *   sv_gconv_bwd_data     dx = conv_transpose(dy, w), written    (wp_bwd; bf16 dx, no accumulate)
+ *   sv_gconv_bwd_weight   dw (+)= dy^T * im2col(x) into the torch layout (f32), through
+ *                         sv_gconv_bwd_weight_nparts(s) per-workgroup f32 partials in `work`
+ *                         (sv_gconv_bwd_weight_work_floats(s) floats) summed in partial order: no atomics,
+ *                         bitwise reproducible.                                                           */
+typedef struct sv_gconv_shape {
+  int32_t B, H, W;      /* input                                  */
+  int32_t C;            /* input = output channels                */
+  int32_t groups;
+  int32_t KH, KW, stride, pad;
+} sv_gconv_shape;
+#define SV_MAX_GPACK_SEGS 32
+typedef struct {
+  const float* w;       /* torch [C][C/groups][3][3] f32          */
+  uint16_t* wp_fwd;     /* [C/32][9][2][64][8] bf16               */
+  uint16_t* wp_bwd;     /* [C/32][9][2][64][8] bf16               */
+  int32_t C, groups;
+} sv_gconv_pack_seg;
+int sv_gconv_weight_pack(const sv_gconv_pack_seg* segs, int32_t nseg, sv_stream_t stream);
+int sv_gconv_fwd(const void* x, const uint16_t* wp_fwd, void* y, const sv_gconv_shape* s, sv_stream_t stream);
+int sv_gconv_bwd_data(const void* dy, const uint16_t* wp_bwd, void* dx, const sv_gconv_shape* s, sv_stream_t stream);
+int sv_gconv_bwd_weight_nparts(const sv_gconv_shape* s);
+int64_t sv_gconv_bwd_weight_work_floats(const sv_gconv_shape* s);
+int sv_gconv_bwd_weight(const void* dy, const void* x, float* work, float* dw, int32_t accumulate,
+                        const sv_gconv_shape* s, sv_stream_t stream);
+
 /* NCHW f32 image [B][C][H][W] -> NHWC [B][H][W][Cs] (dtype), channels >= C zero.                  */
 int sv_image_to_nhwc(const float* img, void* out, int32_t dtype, int32_t B, int32_t C, int32_t H, int32_t W,
                      int32_t Cs, sv_stream_t stream);

@@ -57,7 +57,17 @@ _BN_DUAL = os.environ.get("SV_BN_DUAL", "1") != "0"
 # round-4 layout)
 _GRAD_BF16 = os.environ.get("SV_RESNET_GRAD_BF16", "1") != "0"
 
-RESNET_CFGS = {"resnet18": ("basic", (2, 2, 2, 2)), "resnet50": ("bottleneck", (3, 4, 6, 3))}
+# name -> (block, layers[, groups, base_width]) (timm resnet.py; groups 1, base_width 64 when not given)
+RESNET_CFGS = {
+    "resnet18": ("basic", (2, 2, 2, 2)), "resnet34": ("basic", (3, 4, 6, 3)),
+    "resnet50": ("bottleneck", (3, 4, 6, 3)), "resnet101": ("bottleneck", (3, 4, 23, 3)),
+    "resnet152": ("bottleneck", (3, 8, 36, 3)),
+    # timm's a2 / b / c tags of resnet50 are training recipes of the same architecture
+    "resnet50_a2": ("bottleneck", (3, 4, 6, 3)), "resnet50_b": ("bottleneck", (3, 4, 6, 3)),
+    "resnet50_c": ("bottleneck", (3, 4, 6, 3)),
+    "wide_resnet50": ("bottleneck", (3, 4, 6, 3), 1, 128), "wide_resnet101": ("bottleneck", (3, 4, 23, 3), 1, 128),
+    "resnext50": ("bottleneck", (3, 4, 6, 3), 32, 4),
+}
 _MAX_FORWARD_GRAPHS = 8  # captured forward graphs per model (input signatures beyond that run eagerly)
 BN_EPS = 1e-5
 
@@ -82,13 +92,16 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: nn.Module | None = None) -> None:
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: nn.Module | None = None,
+                 groups: int = 1, base_width: int = 64) -> None:
         super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        # timm Bottleneck: the 3x3's width (wide ResNets: base_width 128; ResNeXt: groups 32 x base_width 4)
+        width = planes * base_width // 64 * groups
+        self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
         self.downsample = downsample
         self.stride = stride
@@ -131,12 +144,16 @@ class _Tape:
 
 
 class ResNetHip(ExplicitBackward, nn.Module):
-    def __init__(self, kind: str = "bottleneck", layers=(3, 4, 6, 3), precision: str = "bf16") -> None:
+    def __init__(self, kind: str = "bottleneck", layers=(3, 4, 6, 3), precision: str = "bf16", groups: int = 1,
+                 base_width: int = 64) -> None:
         super().__init__()
+        if kind == "basic" and (groups != 1 or base_width != 64):
+            raise ValueError("BasicBlock has no groups / base_width (timm: groups=1 and base_width=64 only)")
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
         self.precision = precision
         block = BasicBlock if kind == "basic" else Bottleneck
+        block_kw = {} if kind == "basic" else {"groups": groups, "base_width": base_width}
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         inplanes = 64
@@ -149,7 +166,7 @@ class ResNetHip(ExplicitBackward, nn.Module):
                 if j == 0 and (s != 1 or inplanes != planes * block.expansion):
                     ds = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, stride=s, bias=False),
                                        nn.BatchNorm2d(planes * block.expansion))
-                blocks.append(block(inplanes, planes, s, ds))
+                blocks.append(block(inplanes, planes, s, ds, **block_kw))
                 inplanes = planes * block.expansion
             setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
         self.num_features = inplanes
@@ -215,6 +232,11 @@ class ResNetHip(ExplicitBackward, nn.Module):
         return self.precision == "bf16"
 
     @property
+    def _gconv_native(self) -> bool:
+        """Grouped convs on the grouped kernels (bf16) rather than as their dense embedding (fp32; SV_GCONV=dense)."""
+        return self.compute_bf16 and not K.GCONV_DENSE
+
+    @property
     def act_dtype(self) -> torch.dtype:
         return torch.bfloat16 if self.compute_bf16 else torch.float32
 
@@ -278,9 +300,19 @@ class ResNetHip(ExplicitBackward, nn.Module):
         In train mode (bf16) the conv GEMM's epilogue also emits the following BatchNorm's statistics.
         ``packed``: id(weight) -> its packed form from the forward's one multi-segment pack launch."""
         B, H, W, Cs = x4d.shape
+        if conv.groups > 1 and self._gconv_native:
+            # a grouped 3x3 (ResNeXt conv2) on the grouped kernels; the BatchNorm statistics from K.bn_stats(y)
+            s = K.gconv_shape(B, H, W, Cs, conv.groups, k, stride, pad)
+            wp = packed.get(id(conv.weight)) if packed is not None else None
+            if wp is None:
+                wp, = K.gconv_weight_pack([conv.weight.detach()], conv.groups)
+            return K.gconv_fwd(x4d, wp, s), wp, s, None
         s = K.conv_shape(B, H, W, Cs, conv.weight.shape[0], k, stride, pad, Cin)
         sh = self._shadow
-        if k == 1 and self.compute_bf16 and sh is not None and id(conv.weight) in sh and Cs == conv.weight.shape[1]:
+        if conv.groups > 1 and not (packed is not None and id(conv.weight) in packed):
+            # the dense embedding of a grouped weight (fp32 parity path; bf16: SV_GCONV=dense)
+            wp = K.conv_weight_pack(K.grouped_as_dense(conv.weight.detach(), conv.groups), Cs, self.act_dtype)
+        elif k == 1 and self.compute_bf16 and sh is not None and id(conv.weight) in sh and Cs == conv.weight.shape[1]:
             wp = sh[id(conv.weight)].view(conv.weight.shape[0], 1, Cs)
         elif packed is not None and id(conv.weight) in packed and packed[id(conv.weight)].shape[-1] == Cs:
             wp = packed[id(conv.weight)]
@@ -355,10 +387,19 @@ class ResNetHip(ExplicitBackward, nn.Module):
         packed = None
         if self.compute_bf16 and _MULTI_PACK:
             # every weight the convs below pack (the stem's, the 3x3s') in ONE launch instead of one each
-            ws = [(self.conv1.weight, cs0)] + [(conv.weight, conv.weight.shape[1]) for blk in self.blocks()
-                                               for conv, _, k, _, _, _ in blk.convs() if k > 1]
-            packed = {id(w): wp for (w, _), wp in zip(ws, K.conv_weight_pack_multi(
-                [(w.detach(), c) for w, c in ws], act))}
+            # (a grouped weight's stored channels are its conv's, not weight.shape[1]: it is packed by the grouped
+            # pack launch below or, under SV_GCONV=dense, as its dense embedding)
+            spatial = [conv for blk in self.blocks() for conv, _, k, _, _, _ in blk.convs() if k > 1]
+            grouped = [conv for conv in spatial if conv.groups > 1]
+            dense = [conv for conv in spatial if conv.groups == 1 or not self._gconv_native]
+            ws = [(self.conv1.weight, self.conv1.weight.detach(), cs0)] + [
+                (conv.weight, conv.weight.detach() if conv.groups == 1
+                 else K.grouped_as_dense(conv.weight.detach(), conv.groups), conv.in_channels) for conv in dense]
+            packed = {id(w): wp for (w, _, _), wp in zip(ws, K.conv_weight_pack_multi(
+                [(wd, c) for _, wd, c in ws], act))}
+            if grouped and self._gconv_native:
+                packed.update((id(conv.weight), wp) for conv, wp in zip(grouped, K.gconv_weight_pack(
+                    [conv.weight.detach() for conv in grouped], [conv.groups for conv in grouped])))
         y0, wp0, s0, p0 = self._conv(x0, self.conv1, 7, 2, 3, Cin=3, packed=packed)
         B, H, W, C = y0.shape
         if self._small_bn(y0, p0):
@@ -434,6 +475,21 @@ class ResNetHip(ExplicitBackward, nn.Module):
         return feat, tape
 
     # -- backward ----------------------------------------------------------------------------------
+    @staticmethod
+    def _wgrad(job: tuple, pol: "nv.GemmPolicy | None") -> None:
+        """One weight-gradient job (dy, x, shape, dw, groups), accumulated into dw: the dense implicit GEMM, the grouped
+        kernel (a grouped shape), or -- a grouped conv run as its dense embedding -- the in-group blocks of the dense
+        gradient."""
+        dy4, x, s, dw, groups = job
+        if isinstance(s, nv.GConvShape):
+            K.gconv_bwd_weight(dy4, x, s, dw=dw, accumulate=True)
+        elif groups > 1:
+            dense = torch.zeros(s.Cout, s.Cin, s.KH, s.KW, device=dw.device, dtype=torch.float32)
+            K.conv_bwd_weight(dy4, x, s, dw=dense, accumulate=True, policy=pol)
+            dw += K.dense_group_blocks(dense, groups)
+        else:
+            K.conv_bwd_weight(dy4, x, s, dw=dw, accumulate=True, policy=pol)
+
     def _flush_wgrads(self, jobs: list, params: list, side, keep: list, deferred: list | None = None,
                       pol: "nv.GemmPolicy | None" = None) -> None:
         """Run the block's weight gradients (conv_bwd_weight jobs) and report its parameters ready.  With a
@@ -441,8 +497,8 @@ class ResNetHip(ExplicitBackward, nn.Module):
         grad-ready event it records also covers the BatchNorm gradients), and the operands stay referenced
         in ``keep`` until the streams join (the main stream's allocator may not reuse them earlier)."""
         if side is None:
-            for dy4, x, s, dw in jobs:
-                K.conv_bwd_weight(dy4, x, s, dw=dw, accumulate=True, policy=pol)
+            for job in jobs:
+                self._wgrad(job, pol)
             if deferred is not None:  # reported after the streams join (a bucket may hold side-stream grads)
                 deferred.extend(params)
             else:
@@ -457,8 +513,8 @@ class ResNetHip(ExplicitBackward, nn.Module):
             cap = min(cap, max(1, ncu - self.comm_reserve_cus))
         spol = nv.policy(grid_cap=cap)  # the side stream's own policy, passed with each call
         with torch.cuda.stream(side):
-            for dy4, x, s, dw in jobs:
-                K.conv_bwd_weight(dy4, x, s, dw=dw, accumulate=True, policy=spol)
+            for job in jobs:
+                self._wgrad(job, spol)
             self._ready(params)
         keep.append(jobs)
 
@@ -505,7 +561,7 @@ class ResNetHip(ExplicitBackward, nn.Module):
             conv, bn, _, _, _, _ = convs[ci]
             cur_in, y, mean, rstd, a, wp, s = saved[ci]
             dy4 = dy.view(y.shape)
-            jobs.append((dy4, cur_in, s, g(conv.weight)))
+            jobs.append((dy4, cur_in, s, g(conv.weight), conv.groups))
             params.append(conv.weight)
             if ci == 0:
                 break
@@ -515,11 +571,14 @@ class ResNetHip(ExplicitBackward, nn.Module):
             # the inner BN's backward statistics from the data gradient's GEMM epilogue / split-K finish where
             # that path carries them (bf16; stride 2 on even grids without a split), else from bn_bwd's own
             # statistics pass
-            fused = (K.conv_bwd_data_bn(dy4, wp, s, py, pmean, prstd, pbn.weight, pbn.bias,
-                                        unsplit=_BN_BWD_EPI != "split" or (s.stride == 2 and _S2_BN),
-                                        policy=pol)
-                     if _BN_BWD_EPI != "0" and act == torch.bfloat16 else None)
-            da, bpart = fused if fused is not None else (K.conv_bwd_data(dy4, wp, s, dx_dtype=act, policy=pol), None)
+            if isinstance(s, nv.GConvShape):  # a grouped 3x3: its own data-gradient kernel, the BN's own statistics pass
+                da, bpart = K.gconv_bwd_data(dy4, wp, s), None
+            else:
+                fused = (K.conv_bwd_data_bn(dy4, wp, s, py, pmean, prstd, pbn.weight, pbn.bias,
+                                            unsplit=_BN_BWD_EPI != "split" or (s.stride == 2 and _S2_BN),
+                                            policy=pol)
+                         if _BN_BWD_EPI != "0" and act == torch.bfloat16 else None)
+                da, bpart = fused if fused is not None else (K.conv_bwd_data(dy4, wp, s, dx_dtype=act, policy=pol), None)
             # the inner BN's own ReLU: mask recomputed from y (the activation pa is not read again)
             dy = K.bn_bwd(da.view(-1, Cp), py.view(-1, Cp), pmean, prstd, pbn.weight, relu_beta=pbn.bias.detach(),
                           dgamma=g(pbn.weight), dbeta=g(pbn.bias), dx_dtype=act,
@@ -534,7 +593,7 @@ class ResNetHip(ExplicitBackward, nn.Module):
                 dyd = K.bn_bwd(gm, yd.view(rows, Cq), md, rd, dbn.weight, dgamma=g(dbn.weight), dbeta=g(dbn.bias),
                                dx_dtype=act, batch_stats=batch_stats)
             dyd4 = dyd.view(yd.shape)
-            jobs.append((dyd4, x_in, sd, g(dconv.weight)))
+            jobs.append((dyd4, x_in, sd, g(dconv.weight), 1))
             # conv1's data gradient first (a plain store), then the strided shortcut's added onto the
             # one output parity class its 1x1 taps reach (the other three are skipped, not rewritten)
             dx = K.conv_bwd_data(dy.view(saved[0][1].shape), wp1, s1, dx_dtype=self.grad_dtype, policy=pol)
@@ -588,7 +647,7 @@ class ResNetHip(ExplicitBackward, nn.Module):
                            dgamma=g(self.bn1.weight), dbeta=g(self.bn1.bias), dx_dtype=act,
                            batch_stats=tape.batch_stats)
         self._flush_pending(pending)
-        self._flush_wgrads([(dy0.view(y0.shape), x0, s0, g(self.conv1.weight))],
+        self._flush_wgrads([(dy0.view(y0.shape), x0, s0, g(self.conv1.weight), 1)],
                            [self.conv1.weight, self.bn1.weight, self.bn1.bias], None, keep, deferred, pol)
         if side is not None:
             main.wait_stream(side)  # clip / AdamW / the next step see every side-stream gradient
@@ -600,5 +659,6 @@ def create_resnet(name: str, precision: str = "bf16") -> ResNetHip:
     key = name.split(".")[0]
     if key not in RESNET_CFGS:
         raise ValueError(f"unsupported ResNet variant {name!r}")
-    kind, layers = RESNET_CFGS[key]
-    return ResNetHip(kind, layers, precision=precision)
+    kind, layers, *rest = RESNET_CFGS[key]
+    groups, base_width = rest if rest else (1, 64)
+    return ResNetHip(kind, layers, precision=precision, groups=groups, base_width=base_width)

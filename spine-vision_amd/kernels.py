@@ -1426,6 +1426,116 @@ def conv_bwd_weight(dy: torch.Tensor, x: torch.Tensor, s: nv.ConvShape, *, dw: t
     return dw
 
 
+# ---- grouped 3x3 convolution (ResNeXt conv2; csrc/gconv.hip) ---------------------------------------------------
+# SV_GCONV=dense: the bf16 model runs its grouped convs as the dense embedding through the conv_* wrappers above
+# (the A/B arm; the fp32 model always does, it is the parity path)
+GCONV_DENSE = os.environ.get("SV_GCONV", "") == "dense"
+
+
+def gconv_shape(B, H, W, C, groups, k=3, stride=1, pad=1) -> nv.GConvShape:
+    """sv_gconv_shape of a grouped k x k conv with C_in = C_out = C; raises for a shape csrc/gconv.hip does not take."""
+    _check(groups > 0 and C % groups == 0 and C % 32 == 0 and C // groups in (4, 8, 16, 32) and k == 3 and pad == 1
+           and stride in (1, 2) and B > 0 and H > 0 and W > 0,
+           f"gconv: unsupported shape C={C} groups={groups} k={k} stride={stride} pad={pad} "
+           "(3x3, pad 1, stride 1|2, C % 32 == 0, C / groups in {4, 8, 16, 32})")
+    return nv.GConvShape(B, H, W, C, groups, k, k, stride, pad)
+
+
+def _gconv_out_hw(s: nv.GConvShape) -> tuple[int, int]:
+    return conv_out_hw(s.H, s.W, s.KH, s.stride, s.pad)
+
+
+def gconv_weight_pack(ws: list, groups: int | list) -> list:
+    """Packed forms of grouped weights [C][C/groups][3][3] f32, one launch per SV_MAX_GPACK_SEGS weights
+    (sv_gconv_weight_pack) -> per weight a bf16 tensor [2][C/32][9][2][64][8]: [0] the forward form, [1] the
+    backward-data form (taps flipped, group blocks transposed)."""
+    gs = list(groups) if isinstance(groups, (list, tuple)) else [groups] * len(ws)
+    out = []
+    for i in range(0, len(ws), nv.SV_MAX_GPACK_SEGS):
+        chunk = list(zip(ws[i:i + nv.SV_MAX_GPACK_SEGS], gs[i:i + nv.SV_MAX_GPACK_SEGS]))
+        segs = (nv.GConvPackSeg * len(chunk))()
+        for j, (w, g) in enumerate(chunk):
+            _check(w.dim() == 4 and w.dtype == torch.float32 and w.is_contiguous(),
+                   "gconv_weight_pack: need contiguous f32 [C,C/groups,k,k]")
+            C, Cg, KH, KW = w.shape
+            _check(KH == KW and g > 0 and Cg * g == C, "gconv_weight_pack: weight shape does not match groups")
+            gconv_shape(1, KH, KW, C, g, KH, 1, 1)
+            wp = torch.empty(2, C // 32, 9, 2, 64, 8, device=w.device, dtype=torch.bfloat16)
+            segs[j] = nv.GConvPackSeg(ptr(w), ptr(wp[0]), ptr(wp[1]), C, g)
+            out.append(wp)
+        call("sv_gconv_weight_pack", segs, len(chunk))
+    return out
+
+
+def _gconv_check(t: torch.Tensor, shape: tuple, who: str, what: str) -> None:
+    _check(t.is_contiguous() and tuple(t.shape) == shape and t.dtype == torch.bfloat16 and t.data_ptr() % 16 == 0,
+           f"{who}: {what} must be contiguous 16-byte aligned bf16 {shape}, got {tuple(t.shape)} {t.dtype}")
+
+
+def _gconv_check_wp(wp: torch.Tensor, s: nv.GConvShape, who: str) -> None:
+    _check(tuple(wp.shape) == (2, s.C // 32, 9, 2, 64, 8) and wp.dtype == torch.bfloat16 and wp.is_contiguous(),
+           f"{who}: packed weight must be gconv_weight_pack's [2][C/32][9][2][64][8] bf16")
+
+
+def gconv_fwd(x: torch.Tensor, wp: torch.Tensor, s: nv.GConvShape) -> torch.Tensor:
+    """y = grouped conv(x) over NHWC bf16 (f32 accumulation)."""
+    OH, OW = _gconv_out_hw(s)
+    _gconv_check(x, (s.B, s.H, s.W, s.C), "gconv_fwd", "x")
+    _gconv_check_wp(wp, s, "gconv_fwd")
+    y = torch.empty(s.B, OH, OW, s.C, device=x.device, dtype=torch.bfloat16)
+    _timed_call("gconv", 2.0 * (x.numel() + y.numel()), "sv_gconv_fwd", ptr(x), ptr(wp[0]), ptr(y), ctypes.byref(s))
+    return y
+
+
+def gconv_bwd_data(dy: torch.Tensor, wp: torch.Tensor, s: nv.GConvShape) -> torch.Tensor:
+    """dx = the grouped conv's data gradient (bf16, a fresh buffer)."""
+    OH, OW = _gconv_out_hw(s)
+    _gconv_check(dy, (s.B, OH, OW, s.C), "gconv_bwd_data", "dy")
+    _gconv_check_wp(wp, s, "gconv_bwd_data")
+    dx = torch.empty(s.B, s.H, s.W, s.C, device=dy.device, dtype=torch.bfloat16)
+    _timed_call("gconv", 2.0 * (dx.numel() + dy.numel()), "sv_gconv_bwd_data", ptr(dy), ptr(wp[1]), ptr(dx),
+                ctypes.byref(s))
+    return dx
+
+
+def gconv_bwd_weight(dy: torch.Tensor, x: torch.Tensor, s: nv.GConvShape, *, dw: torch.Tensor,
+                     accumulate: bool = True) -> torch.Tensor:
+    """dw (+)= the grouped conv's weight gradient, torch layout [C][C/groups][3][3] f32."""
+    OH, OW = _gconv_out_hw(s)
+    _gconv_check(x, (s.B, s.H, s.W, s.C), "gconv_bwd_weight", "x")
+    _gconv_check(dy, (s.B, OH, OW, s.C), "gconv_bwd_weight", "dy")
+    _check(dw.dtype == torch.float32 and dw.is_contiguous() and tuple(dw.shape) == (s.C, s.C // s.groups, 3, 3),
+           "gconv_bwd_weight: dw must be f32 [C,C/groups,3,3]")
+    nwork = value("sv_gconv_bwd_weight_work_floats", ctypes.byref(s))
+    work = torch.empty(nwork, device=dy.device, dtype=torch.float32)
+    _timed_call("gconv", 2.0 * (x.numel() + dy.numel()) + 8.0 * nwork, "sv_gconv_bwd_weight", ptr(dy), ptr(x),
+                ptr(work), ptr(dw), int(accumulate), ctypes.byref(s))
+    return dw
+
+
+def grouped_as_dense(w: torch.Tensor, groups: int | None = None) -> torch.Tensor:
+    """A grouped weight [C][Cg][k][k] embedded block-diagonally in the dense [C][C][k][k] weight of the same
+    convolution (zeros across groups): the fp32 parity path of grouped convs and the SV_GCONV=dense arm run it through
+    conv_fwd / conv_bwd_data / conv_bwd_weight."""
+    C, Cg = w.shape[0], w.shape[1]
+    g = C // Cg if groups is None else groups
+    _check(g * Cg == C, "grouped_as_dense: weight shape does not match groups")
+    dense = w.new_zeros(g, Cg, g, Cg, *w.shape[2:])
+    idx = torch.arange(g, device=w.device)
+    dense[idx, :, idx] = w.reshape(g, Cg, Cg, *w.shape[2:])
+    return dense.view(C, C, *w.shape[2:])
+
+
+def dense_group_blocks(dense: torch.Tensor, groups: int) -> torch.Tensor:
+    """The in-group blocks [C][C/groups][k][k] of a dense [C][C][k][k] weight (gradient): grouped_as_dense's inverse."""
+    C = dense.shape[0]
+    Cg = C // groups
+    _check(groups * Cg == C and dense.shape[1] == C, "dense_group_blocks: shape does not match groups")
+    idx = torch.arange(groups, device=dense.device)
+    v = dense.reshape(groups, Cg, groups, Cg, *dense.shape[2:])
+    return v[idx, :, idx].reshape(C, Cg, *dense.shape[2:]).contiguous()
+
+
 def image_u8_hwc_to_nhwc(img_u8: torch.Tensor, Cs: int, dtype: torch.dtype, *, mean=IMAGENET_MEAN,
                          std=IMAGENET_STD) -> torch.Tensor:
     """Device form of the classification transform tail (row f1): collated uint8 crops [B,H,W,3]

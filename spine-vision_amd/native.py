@@ -104,6 +104,19 @@ class ConvShape(ctypes.Structure):
                 ("stride", _i32), ("pad", _i32), ("Cin", _i32)]
 
 
+class GConvShape(ctypes.Structure):
+    """sv_gconv_shape (include/sv_kernels.h): a grouped 3x3 convolution with C_in = C_out = C."""
+    _fields_ = [("B", _i32), ("H", _i32), ("W", _i32), ("C", _i32), ("groups", _i32), ("KH", _i32), ("KW", _i32),
+                ("stride", _i32), ("pad", _i32)]
+
+
+class GConvPackSeg(ctypes.Structure):
+    """sv_gconv_pack_seg (include/sv_kernels.h): one weight of sv_gconv_weight_pack."""
+    _fields_ = [("w", _p), ("wp_fwd", _p), ("wp_bwd", _p), ("C", _i32), ("groups", _i32)]
+
+
+SV_MAX_GPACK_SEGS = 32
+_GS = ctypes.POINTER(GConvShape)
 _CS = ctypes.POINTER(ConvShape)
 _POL = ctypes.POINTER(GemmPolicy)
 
@@ -185,6 +198,12 @@ _SIGS = {
     "sv_conv_bwd_data_bn": [_p, _p, _p, _i32, _CS, _p, ctypes.POINTER(BnRef), _p, _p, _i32, _POL, _p],
     "sv_conv_bwd_weight_work_floats": [_CS],
     "sv_conv_bwd_weight": [_p, _p, _p, _p, _i32, _i32, _CS, _POL, _p],
+    "sv_gconv_weight_pack": [ctypes.POINTER(GConvPackSeg), _i32, _p],
+    "sv_gconv_fwd": [_p, _p, _p, _GS, _p],
+    "sv_gconv_bwd_data": [_p, _p, _p, _GS, _p],
+    "sv_gconv_bwd_weight_nparts": [_GS],
+    "sv_gconv_bwd_weight_work_floats": [_GS],
+    "sv_gconv_bwd_weight": [_p, _p, _p, _p, _i32, _GS, _p],
     "sv_image_to_nhwc": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_image_u8_hwc_to_nhwc": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_bn_nparts": [_i64, _i32],
@@ -221,10 +240,11 @@ _SIGS = {
     "sv_avgpool_bwd": [_p, _p, _i32, _i32, _i32, _i32, _p],
 }
 _RESTYPES = {"sv_last_error_string": ctypes.c_char_p, "sv_build_target": ctypes.c_char_p,
-             "sv_conv_bwd_weight_work_floats": ctypes.c_int64}
+             "sv_conv_bwd_weight_work_floats": ctypes.c_int64, "sv_gconv_bwd_weight_work_floats": ctypes.c_int64}
 # entry points that return a value (size / count) rather than an sv_status
 _VALUE_FNS = {n for n in _SIGS if n.endswith(("_nparts", "_ws"))} | {"sv_version", "sv_bn_fold_ok", "sv_dwconv7_ln_fused_ok", "sv_conv_bwd_weight_work_floats",
-                                                                     "sv_stream_create_cu_reserved", "sv_bn_small_ok"}
+                                                                     "sv_stream_create_cu_reserved", "sv_bn_small_ok",
+                                                                     "sv_gconv_bwd_weight_work_floats"}
 
 # entry points that take no stream (call() appends none) but return an sv_status
 _NOSTREAM_FNS = {"sv_ctx_create", "sv_ctx_destroy", "sv_ctx_get_info"}

@@ -4,9 +4,11 @@
 
 Here ``create`` returns the MI355X-native module (HIP kernels, timm module tree and state_dict keys)
 for the backbones on the north-star path -- ConvNeXt-tiny/small/base/large and ConvNeXt V2-base/large
-(localization) and ResNet-18/50 (classification).  Every other name of the reference registry is
-recognised (``list_backbones`` returns the reference's full list) but raises: those families (and
-ConvNeXt-xlarge and the other ConvNeXt V2 sizes) are outside this build's scope.
+(localization) and the ResNet family (classification): ResNet-18/34/50/101/152, the ``resnet50_a2`` / ``_b`` /
+``_c`` recipes of ResNet-50, Wide-ResNet-50/101 and ResNeXt-50 (32x4d, its grouped 3x3 on csrc/gconv.hip).  Every
+other name of the reference registry is recognised (``list_backbones`` returns the reference's full list) but
+raises: those families (and ConvNeXt-xlarge, the other ConvNeXt V2 sizes, ``resnext101``, ``resnet50_d`` and
+``resnetrs*``) are outside this build's scope.
 ``pretrained=True`` cannot download weights offline; pass ``pretrained=False`` or load a timm
 state_dict with ``load_state_dict`` (keys match).
 """
@@ -54,9 +56,12 @@ BACKBONES: dict[str, str] = {k: v for fam in _FAMILIES.values() for k, v in fam.
 
 # names built natively on MI355X (the north-star backbones)
 NATIVE = ("convnext_tiny", "convnext_small", "convnext_base", "convnext_large", "convnextv2_base", "convnextv2_large",
-          "resnet18", "resnet50")
+          "resnet18", "resnet50", "resnet34", "resnet101", "resnet152", "resnet50_a2", "resnet50_b", "resnet50_c",
+          "wide_resnet50", "wide_resnet101", "resnext50")
 _FEATURE_DIMS = {"convnext_tiny": 768, "convnext_small": 768, "convnext_base": 1024, "convnext_large": 1536, "convnextv2_base": 1024, "convnextv2_large": 1536,
-                 "resnet18": 512, "resnet50": 2048}
+                 "resnet18": 512, "resnet50": 2048, "resnet34": 512, "resnet101": 2048, "resnet152": 2048,
+                 "resnet50_a2": 2048, "resnet50_b": 2048, "resnet50_c": 2048, "wide_resnet50": 2048,
+                 "wide_resnet101": 2048, "resnext50": 2048}
 
 
 class BackboneFactory:
