@@ -339,7 +339,7 @@ int sv_stem_patchify_ln_bwd(const float* img, const float* w, const float* b, co
  * (training/datasets/localization.py:196-233, 254: convert("RGB") -> ToTensor -> Normalize) is
  * applied in flight as (u / 255 - mean[c]) / std[c] in f32.  norm_mean / norm_std: HOST float[3]
  * (ignored for SV_IMG_F32_NCHW, may be NULL).                                                      */
-typedef enum { SV_IMG_F32_NCHW = 0, SV_IMG_U8_GRAY = 1 } sv_image_kind;
+typedef enum { SV_IMG_F32_NCHW = 0, SV_IMG_U8_GRAY = 1, SV_IMG_U8_HWC = 2 /* sv_patchify16 only */ } sv_image_kind;
 int sv_stem_patchify(const void* img, int32_t img_kind, const float* norm_mean, const float* norm_std,
                      uint16_t* patches, int32_t B, int32_t H, int32_t W, sv_stream_t stream);
 int sv_stem_weight_pack(const float* w, uint16_t* wpack, int32_t C, sv_stream_t stream);
@@ -609,6 +609,41 @@ int sv_gconv_bwd_weight_nparts(const sv_gconv_shape* s);
 int64_t sv_gconv_bwd_weight_work_floats(const sv_gconv_shape* s);
 int sv_gconv_bwd_weight(const void* dy, const void* x, float* work, float* dw, int32_t accumulate,
                         const sv_gconv_shape* s, sv_stream_t stream);
+
+/* ---- fused multi-head self-attention (csrc/attn.hip) ---------------------------------------------
+ * Replaces timm Attention's softmax(q k^T * scale) v (VisionTransformer blocks, head dimension 64) and its autograd
+ * backward, between the qkv and proj Linears, on the layouts those GEMMs store and read (no permute, no copy):
+ *   qkv / dqkv  bf16 [B][img_rows][3 * heads * 64]  columns ordered (q|k|v, head, d)
+ *   out / dout  bf16 [B][img_rows][heads * 64]      heads concatenated on the channel axis
+ *   lse         f32  [B][heads][N]                  row log-sum-exp of the scaled scores (the backward's input)
+ * An image owns img_rows >= N rows of each matrix (0 = N: the unpadded contract); only its first N rows are tokens.
+ * Rows N .. img_rows - 1 are never read, and are written as zeros in `out` (forward) and `dqkv` (backward).
+ * bf16 MFMA with f32 accumulation, f32 softmax, P rounded to bf16 once before P v; the backward recomputes P from
+ * lse, D = rowsum(dout . out).  The N x N matrices never reach HBM.  One workgroup owns an (image, head)'s dk and dv
+ * and sums dq in a fixed order: no atomics, bitwise reproducible, and an image's result does not depend on the batch.
+ * N in [1, 256]; N > 256 or head_dim != 64: SV_ERR_UNSUPPORTED before any launch.  qkv / out / dout / dqkv 16-byte
+ * aligned.  scale > 0 (timm: head_dim^-0.5 = 0.125).                                                            */
+int sv_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int32_t B, int32_t N, int64_t img_rows, int32_t heads,
+                int32_t head_dim, float scale, sv_stream_t stream);
+int sv_attn_bwd(const uint16_t* qkv, const uint16_t* out, const float* lse, const uint16_t* dout, uint16_t* dqkv,
+                int32_t B, int32_t N, int64_t img_rows, int32_t heads, int32_t head_dim, float scale,
+                sv_stream_t stream);
+
+/* ---- ViT / DeiT-III patch embedding operand and token assembly (csrc/vit.hip) --------------------
+ * sv_patchify16: the rows of timm PatchEmbed's Conv2d(3, C, 16, stride 16) as a GEMM operand: 768 wide,
+ * k = ci * 256 + ky * 16 + kx (proj.weight [C,3,16,16] flattened, so the weight is the B operand as stored), patches
+ * in row-major order; image b's patch p is row b * rows_per_img + row0 + p (rows_per_img = 0: the patch count, i.e.
+ * the plain [B * P][768] matrix); other rows are left untouched.  img_kind: SV_IMG_F32_NCHW [B,3,H,W] (normalised),
+ * SV_IMG_U8_GRAY [B,H,W] or SV_IMG_U8_HWC [B,H,W,3]; the uint8 kinds apply (u / 255 - mean[c]) / std[c] in f32
+ * (norm_mean / norm_std: HOST float[3]).  out_dtype SV_BF16 or SV_F32.  H, W multiples of 16.
+ * sv_vit_tokens: the token matrix x [B][rows_per_img][C] f32 from the patch-embedding output pe (same rows):
+ * row 0 = cls (+ pos[0] when pos_has_cls: ViT; DeiT-III's pos [P][C] covers the patches only), rows 1..P =
+ * pe + pos, rows > P zero.                                                                                      */
+int sv_patchify16(const void* img, int32_t img_kind, const float* norm_mean, const float* norm_std, void* patches,
+                  int32_t out_dtype, int32_t B, int32_t H, int32_t W, int64_t rows_per_img, int32_t row0,
+                  sv_stream_t stream);
+int sv_vit_tokens(const float* pe, const float* cls, const float* pos, float* x, int32_t B, int32_t P,
+                  int32_t rows_per_img, int32_t C, int32_t pos_has_cls, sv_stream_t stream);
 
 /* NCHW f32 image [B][C][H][W] -> NHWC [B][H][W][Cs] (dtype), channels >= C zero.                  */
 int sv_image_to_nhwc(const float* img, void* out, int32_t dtype, int32_t B, int32_t C, int32_t H, int32_t W,

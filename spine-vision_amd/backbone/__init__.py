@@ -2,5 +2,7 @@
 
 from .convnext import CONVNEXT_CFGS, ConvNeXtHip, create_convnext
 from .resnet import RESNET_CFGS, ResNetHip, create_resnet
+from .vit import VIT_CFGS, ViTHip, create_vit
 
-__all__ = ["CONVNEXT_CFGS", "ConvNeXtHip", "create_convnext", "RESNET_CFGS", "ResNetHip", "create_resnet"]
+__all__ = ["CONVNEXT_CFGS", "ConvNeXtHip", "create_convnext", "RESNET_CFGS", "ResNetHip", "create_resnet",
+           "VIT_CFGS", "ViTHip", "create_vit"]

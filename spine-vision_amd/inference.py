@@ -36,7 +36,10 @@ def normalize_to_uint8(arr: np.ndarray) -> np.ndarray:
 
 
 def _backbone_name(variant: str) -> str:
-    # cropping.py:424-428
+    # cropping.py:424-428; a full registry name of another family ("vit_base", "deit_small": 224x224 images only)
+    # passes through
+    if variant.startswith(("vit_", "deit_")):
+        return variant
     return f"convnext_{variant}" if not variant.startswith("v2_") else f"convnextv2_{variant[3:]}"
 
 

@@ -638,6 +638,142 @@ def layernorm_bwd(dy2d, x2d, mean, rstd, w, *, dw, db, dx=None, accumulate_dx=Fa
 
 
 # ----------------------------------------------------------------------------------------------
+# Multi-head self-attention (ViT / DeiT-III, csrc/attn.hip)
+# SV_ATTN=torch: the same maths as torch ops on views of the same buffers (A/B and parity arm, in the style of
+# SV_GCONV=dense): matmul -> f32 softmax -> bf16 -> matmul, and an explicit backward from the same formulas (no
+# autograd).  The two products that feed f32 maths (q k^T and dout v^T) take f32 copies of the bf16 operands, so they
+# are summed in f32 like the kernel's accumulators; the three that consume the bf16 P / dS are bf16 matmuls.  f32 operands (precision="fp32") always take this arm, in f32 throughout: attention is the one part of
+# the fp32 parity mode that does not run on this library.
+ATTN_TORCH = os.environ.get("SV_ATTN", "") == "torch"
+ATTN_HEAD_DIM = 64
+ATTN_MAX_N = 256
+
+
+def _attn_geometry(who: str, qkv, B: int, N: int, heads: int, img_rows) -> tuple[int, int]:
+    rows = N if img_rows is None else int(img_rows)
+    C = heads * ATTN_HEAD_DIM
+    _check(B > 0 and heads > 0 and 1 <= N <= rows, f"{who}: need B, heads > 0 and 1 <= N <= img_rows")
+    _check(qkv.dim() == 2 and tuple(qkv.shape) == (B * rows, 3 * C) and qkv.is_contiguous()
+           and qkv.dtype in (torch.bfloat16, torch.float32),
+           f"{who}: qkv must be contiguous bf16 / f32 [{B * rows}, {3 * C}], got {tuple(qkv.shape)} {qkv.dtype}")
+    return rows, C
+
+
+def _attn_views(t2d, B: int, rows: int, N: int, heads: int, parts: int):
+    """[B * rows, parts * heads * 64] -> `parts` views [B, heads, N, 64] (no copy)."""
+    v = t2d.view(B, rows, parts, heads, ATTN_HEAD_DIM)[:, :N].permute(2, 0, 3, 1, 4)
+    return tuple(v[i] for i in range(parts))
+
+
+def _attn_torch_arm(qkv) -> bool:
+    return ATTN_TORCH or qkv.dtype == torch.float32
+
+
+def attn_fwd(qkv, B: int, N: int, heads: int, *, img_rows: int | None = None, scale: float | None = None,
+             out: torch.Tensor | None = None, lse: torch.Tensor | None = None, torch_arm: bool | None = None):
+    """(out [B * img_rows, heads * 64], lse f32 [B, heads, N]) = softmax(q k^T * scale) v per (image, head) of
+    qkv [B * img_rows, 3 * heads * 64] (columns (q|k|v, head, d); an image's first N rows are its tokens, the other
+    rows padding: not read, zero in ``out``).  bf16 operands run sv_attn_fwd unless ``torch_arm`` (default: the
+    SV_ATTN=torch switch); f32 operands always run the torch arm in f32."""
+    rows, C = _attn_geometry("attn_fwd", qkv, B, N, heads, img_rows)
+    scale = ATTN_HEAD_DIM ** -0.5 if scale is None else float(scale)
+    if out is None:
+        out = torch.empty(B * rows, C, device=qkv.device, dtype=qkv.dtype)
+    if lse is None:
+        lse = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32)
+    _check(tuple(out.shape) == (B * rows, C) and out.is_contiguous() and out.dtype == qkv.dtype, "attn_fwd: bad out")
+    _check(tuple(lse.shape) == (B, heads, N) and lse.is_contiguous() and lse.dtype == torch.float32, "attn_fwd: bad lse")
+    if _attn_torch_arm(qkv) if torch_arm is None else (torch_arm or qkv.dtype == torch.float32):
+        q, k, v = _attn_views(qkv, B, rows, N, heads, 3)
+        s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+        torch.logsumexp(s, dim=-1, out=lse)
+        p = torch.exp(s - lse.unsqueeze(-1)).to(qkv.dtype)
+        o = out.view(B, rows, heads, ATTN_HEAD_DIM)
+        o[:, :N] = torch.matmul(p, v).permute(0, 2, 1, 3)
+        if rows > N:
+            o[:, N:] = 0
+        return out, lse
+    _check(N <= ATTN_MAX_N, f"attn_fwd: N = {N} tokens (at most {ATTN_MAX_N})")
+    call("sv_attn_fwd", ptr(qkv), ptr(out), ptr(lse), B, N, rows, heads, ATTN_HEAD_DIM, scale)
+    return out, lse
+
+
+def attn_bwd(qkv, out, lse, dout, B: int, N: int, heads: int, *, img_rows: int | None = None,
+             scale: float | None = None, dqkv: torch.Tensor | None = None, torch_arm: bool | None = None):
+    """dqkv [B * img_rows, 3 * heads * 64] from dout [B * img_rows, heads * 64]: P recomputed from ``lse``,
+    D = rowsum(dout . out), dv = P^T dout, dS = P (dout v^T - D) scale, dq = dS k, dk = dS^T q (pad rows zero)."""
+    rows, C = _attn_geometry("attn_bwd", qkv, B, N, heads, img_rows)
+    scale = ATTN_HEAD_DIM ** -0.5 if scale is None else float(scale)
+    for name, t_ in (("out", out), ("dout", dout)):
+        _check(tuple(t_.shape) == (B * rows, C) and t_.is_contiguous() and t_.dtype == qkv.dtype, f"attn_bwd: bad {name}")
+    _check(tuple(lse.shape) == (B, heads, N) and lse.is_contiguous() and lse.dtype == torch.float32, "attn_bwd: bad lse")
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    _check(dqkv.shape == qkv.shape and dqkv.is_contiguous() and dqkv.dtype == qkv.dtype, "attn_bwd: bad dqkv")
+    if _attn_torch_arm(qkv) if torch_arm is None else (torch_arm or qkv.dtype == torch.float32):
+        q, k, v = _attn_views(qkv, B, rows, N, heads, 3)
+        (o,), (do,) = _attn_views(out, B, rows, N, heads, 1), _attn_views(dout, B, rows, N, heads, 1)
+        p = torch.exp(torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale - lse.unsqueeze(-1))
+        dp = torch.matmul(do.float(), v.float().transpose(-1, -2))
+        dsum = (do.float() * o.float()).sum(-1, keepdim=True)
+        ds = (p * (dp - dsum) * scale).to(qkv.dtype)
+        g = dqkv.view(B, rows, 3, heads, ATTN_HEAD_DIM)
+        g[:, :N, 0] = torch.matmul(ds, k).permute(0, 2, 1, 3)
+        g[:, :N, 1] = torch.matmul(ds.transpose(-1, -2), q).permute(0, 2, 1, 3)
+        g[:, :N, 2] = torch.matmul(p.to(qkv.dtype).transpose(-1, -2), do).permute(0, 2, 1, 3)
+        if rows > N:
+            g[:, N:] = 0
+        return dqkv
+    _check(N <= ATTN_MAX_N, f"attn_bwd: N = {N} tokens (at most {ATTN_MAX_N})")
+    call("sv_attn_bwd", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), B, N, rows, heads, ATTN_HEAD_DIM, scale)
+    return dqkv
+
+
+def patchify16(img, *, out_dtype, rows_per_img: int | None = None, row0: int = 0, out: torch.Tensor | None = None,
+               mean=None, std=None) -> torch.Tensor:
+    """The 16x16 patch rows of a batch as the patch-embedding GEMM's A operand (sv_patchify16): [B * rows_per_img, 768],
+    k = (c, ky, kx) -- ``patch_embed.proj.weight.view(C, 768)`` is the B operand as stored; image b's patch p is row
+    b * rows_per_img + row0 + p (default: the plain [B * P, 768] matrix).  ``img``: f32 [B,3,H,W] (normalised), uint8
+    [B,H,W,3] (classification: ToTensor + Normalize in flight) or uint8 [B,H,W] (localization: also gray -> RGB).
+    With ``rows_per_img`` larger than the patch count the other rows are zeros (a fresh buffer) or kept (``out``)."""
+    if img.dtype == torch.uint8:
+        _check(img.is_contiguous() and (img.dim() == 3 or (img.dim() == 4 and img.shape[-1] == 3)),
+               "patchify16: uint8 input must be contiguous [B,H,W] or [B,H,W,3]")
+        B, H, W = img.shape[:3]
+        kind = nv.SV_IMG_U8_GRAY if img.dim() == 3 else nv.SV_IMG_U8_HWC
+    else:
+        _check(img.dim() == 4 and img.shape[1] == 3 and img.dtype == torch.float32 and img.is_contiguous(),
+               "patchify16: expects contiguous f32 [B,3,H,W]")
+        B, _, H, W = img.shape
+        kind = nv.SV_IMG_F32_NCHW
+    _check(H % 16 == 0 and W % 16 == 0 and H > 0 and W > 0, "patchify16: H, W must be multiples of 16")
+    P = (H // 16) * (W // 16)
+    rows = P if rows_per_img is None else int(rows_per_img)
+    _check(row0 >= 0 and rows >= row0 + P, "patchify16: rows_per_img must hold row0 + the patch rows")
+    if out is None:
+        alloc = torch.empty if rows == P else torch.zeros
+        out = alloc(B * rows, 768, device=img.device, dtype=out_dtype)
+    _check(tuple(out.shape) == (B * rows, 768) and out.is_contiguous() and out.dtype == out_dtype, "patchify16: bad out")
+    call("sv_patchify16", ptr(img), kind, _host3(IMAGENET_MEAN if mean is None else mean),
+         _host3(IMAGENET_STD if std is None else std), ptr(out), dt(out), B, H, W, rows, row0)
+    return out
+
+
+def vit_tokens(pe: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, B: int, P: int, rows_per_img: int,
+               pos_has_cls: bool) -> torch.Tensor:
+    """The token matrix [B * rows_per_img, C] f32 (sv_vit_tokens): per image row 0 the class token (+ pos[0] for ViT),
+    rows 1..P the patch embeddings ``pe`` (same row layout) + their position embedding, the rest zero."""
+    C = pe.shape[1]
+    _check(tuple(pe.shape) == (B * rows_per_img, C) and pe.dtype == torch.float32 and pe.is_contiguous(),
+           "vit_tokens: pe must be contiguous f32 [B * rows_per_img, C]")
+    _check(cls.numel() == C and pos.numel() == (P + int(bool(pos_has_cls))) * C and cls.dtype == pos.dtype == torch.float32
+           and cls.is_contiguous() and pos.is_contiguous(), "vit_tokens: bad cls / pos")
+    x = torch.empty_like(pe)
+    call("sv_vit_tokens", ptr(pe), ptr(cls), ptr(pos), ptr(x), B, P, rows_per_img, C, int(bool(pos_has_cls)))
+    return x
+
+
+# ----------------------------------------------------------------------------------------------
 # Global Response Normalization (ConvNeXt V2, csrc/grn.hip)
 EPS_GRN = 1e-6
 

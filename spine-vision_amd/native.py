@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SV_LIB_PATH") or os.path.join(_HERE, "libsv_kernels.s
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "sv_kernels.h")
 
 SV_F32, SV_BF16 = 0, 1
-SV_IMG_F32_NCHW, SV_IMG_U8_GRAY = 0, 1
+SV_IMG_F32_NCHW, SV_IMG_U8_GRAY, SV_IMG_U8_HWC = 0, 1, 2
 SV_BN_SMALL_MASK, SV_BN_SMALL_RELU, SV_BN_SMALL_DUAL = 0, 1, 2
 SV_HEAD_CE, SV_HEAD_BCE = 0, 1
 SV_BN_FOLD_CTL_INTS, SV_BN_FOLD_WS_FLOATS = 256, 2 * 2 * 2048 + 2 * 64 * 16 * 64  # include/sv_kernels.h
@@ -204,6 +204,11 @@ _SIGS = {
     "sv_gconv_bwd_weight_nparts": [_GS],
     "sv_gconv_bwd_weight_work_floats": [_GS],
     "sv_gconv_bwd_weight": [_p, _p, _p, _p, _i32, _GS, _p],
+    # ViT / DeiT-III
+    "sv_attn_fwd": [_p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
+    "sv_attn_bwd": [_p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
+    "sv_patchify16": [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i64, _i32, _p],
+    "sv_vit_tokens": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_image_to_nhwc": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_image_u8_hwc_to_nhwc": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_bn_nparts": [_i64, _i32],
