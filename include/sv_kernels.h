@@ -629,6 +629,20 @@ int sv_attn_bwd(const uint16_t* qkv, const uint16_t* out, const float* lse, cons
                 int32_t B, int32_t N, int64_t img_rows, int32_t heads, int32_t head_dim, float scale,
                 sv_stream_t stream);
 
+/* ---- streaming attention for N up to 2048 (csrc/attn_stream.hip) -----------------------------------
+ * The same maths, layouts, padding contract and number formats as sv_attn_fwd / sv_attn_bwd, with the other side of
+ * the N x N matrix streamed through LDS in 64-token tiles: the forward keeps a running max, a running sum and a
+ * rescaled accumulator per query (one pass over K and V); the backward is a D = rowsum(dout . out) pre-pass, a
+ * dk / dv kernel (workgroup per 128 keys) and a dq kernel (workgroup per 128 queries), every element owned by one
+ * wave that sums in a fixed order: no atomics, bitwise reproducible, independent of the batch.
+ * `dws`: f32 [B][heads][N] workspace of the backward (D), allocated by the caller; the library allocates nothing.
+ * N in [1, 2048]; N > 2048 or head_dim != 64: SV_ERR_UNSUPPORTED before any launch.                               */
+int sv_attn_stream_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int32_t B, int32_t N, int64_t img_rows,
+                       int32_t heads, int32_t head_dim, float scale, sv_stream_t stream);
+int sv_attn_stream_bwd(const uint16_t* qkv, const uint16_t* out, const float* lse, const uint16_t* dout,
+                       uint16_t* dqkv, float* dws, int32_t B, int32_t N, int64_t img_rows, int32_t heads,
+                       int32_t head_dim, float scale, sv_stream_t stream);
+
 /* ---- ViT / DeiT-III patch embedding operand and token assembly (csrc/vit.hip) --------------------
  * sv_patchify16: the rows of timm PatchEmbed's Conv2d(3, C, 16, stride 16) as a GEMM operand: 768 wide,
  * k = ci * 256 + ky * 16 + kx (proj.weight [C,3,16,16] flattened, so the weight is the B operand as stored), patches

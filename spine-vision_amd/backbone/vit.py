@@ -9,16 +9,19 @@ against): ``VisionTransformer`` with patch 16, ``qkv_bias=True``, MLP ratio 4, e
 ``global_pool='token'``, no dropout / drop-path, head dimension 64; DeiT-III adds LayerScale (``ls1`` / ``ls2``,
 init 1e-6) and ``no_embed_class`` (the position embedding covers the patches only and is added before the class
 token is prepended).  These timm models are strict about the image size: an input that is not ``img_size`` x
-``img_size`` raises ``ValueError``.
+``img_size`` raises ``ValueError``.  ``img_size`` is any multiple of 16 up to 2048 tokens (224: 197 tokens, 256: 257,
+384: 577, 512: 1025; default: env ``SV_VIT_IMG_SIZE``, else 224); a state_dict saved at another square size loads
+with its ``pos_embed`` resampled (``resample_abs_pos_embed``).
 
 * Same module tree and ``state_dict`` keys as timm (``cls_token``, ``pos_embed``, ``patch_embed.proj``,
   ``blocks.i.{norm1,attn.qkv,attn.proj,ls1,norm2,mlp.fc1,mlp.fc2,ls2}``, ``norm``), ``num_features``,
   ``forward([B,3,H,W] f32 | uint8 [B,H,W,3] | uint8 [B,H,W]) -> [B, C]`` (the class-token row of the final norm).
   The sub-modules are parameter containers only; their own ``forward`` is never called.
 * Forward and backward are explicit kernel sequences over a token matrix [B * Np, C] (DESIGN.md "ViT / DeiT-III"):
-  ``sv_patchify16`` -> patch GEMM -> ``sv_vit_tokens``; per block LayerNorm -> qkv GEMM (+bias) -> ``sv_attn_fwd`` ->
-  proj GEMM (+bias, *gamma, +residual) -> LayerNorm -> fc1 GEMM (+bias, GELU and GELU') -> fc2 GEMM (+bias, *gamma,
-  +residual); the final LayerNorm over the class rows only.  ViT has no layer scale: its two residual epilogues get a
+  ``sv_patchify16`` -> patch GEMM -> ``sv_vit_tokens``; per block LayerNorm -> qkv GEMM (+bias) -> ``sv_attn_fwd``
+  (up to 256 tokens; above, or with ``SV_ATTN=stream``, ``sv_attn_stream_fwd``: DESIGN.md "ViT / DeiT-III at 256-512
+  px") -> proj GEMM (+bias, *gamma, +residual) -> LayerNorm -> fc1 GEMM (+bias, GELU and GELU') -> fc2 GEMM (+bias,
+  *gamma, +residual); the final LayerNorm over the class rows only.  ViT has no layer scale: its two residual epilogues get a
   buffer of ones that is not in the state_dict (as ConvNeXt V2's fc2).
 * Row layout: every image owns Np = N rounded up to a multiple of 8 rows (N = 197 tokens -> 200), so every GEMM and
   LayerNorm row count stays a multiple of 8, the ground those kernels were built and tested on.  Pad rows are zero
@@ -37,12 +40,15 @@ token is prepended).  These timm models are strict about the image size: an inpu
 
 from __future__ import annotations
 
+import logging
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Callable
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import kernels as K
 from .. import native as nv
@@ -61,6 +67,8 @@ VIT_CFGS = {
 }
 PATCH = 16
 HEAD_DIM = 64
+_log = logging.getLogger(__name__)
+_RESAMPLE_LOGGED = False
 
 
 class _PatchEmbed(nn.Module):
@@ -159,12 +167,17 @@ class _Wgrads:
 
 class ViTHip(ExplicitBackward, nn.Module):
     def __init__(self, dim: int = 768, depth: int = 12, heads: int = 12, ls_init: float | None = None,
-                 no_embed_class: bool = False, img_size: int = 224, precision: str = "bf16") -> None:
+                 no_embed_class: bool = False, img_size: int | tuple[int, int] = 224, precision: str = "bf16") -> None:
         super().__init__()
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
         if dim != heads * HEAD_DIM:
             raise ValueError(f"head dimension must be {HEAD_DIM}: dim {dim} with {heads} heads")
+        if isinstance(img_size, (tuple, list)):
+            if len(img_size) != 2 or img_size[0] != img_size[1]:
+                raise ValueError(f"img_size must be square, got {tuple(img_size)}")
+            img_size = img_size[0]
+        img_size = int(img_size)
         if img_size % PATCH or img_size <= 0:
             raise ValueError(f"img_size must be a positive multiple of {PATCH}, got {img_size}")
         self.dim, self.depth, self.heads = dim, depth, heads
@@ -172,9 +185,12 @@ class ViTHip(ExplicitBackward, nn.Module):
         self.img_size = img_size
         self.num_patches = (img_size // PATCH) ** 2
         self.num_tokens = self.num_patches + 1
-        if self.num_tokens > K.ATTN_MAX_N:
+        if self.num_tokens > K.ATTN_STREAM_MAX_N:
             raise ValueError(f"img_size {img_size}: {self.num_tokens} tokens, the attention kernels hold at most "
-                             f"{K.ATTN_MAX_N}")
+                             f"{K.ATTN_STREAM_MAX_N}")
+        # up to 256 tokens (224 px) the one-pass kernels of csrc/attn.hip, above that the streaming pair of
+        # csrc/attn_stream.hip; SV_ATTN=stream (or this attribute) forces the streaming pair at any size (A/B runs)
+        self.attn_stream = os.environ.get("SV_ATTN", "") == "stream"
         self.rows_per_img = -(-self.num_tokens // 8) * 8  # Np: tokens padded to a multiple of 8 rows
         self.precision = precision
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
@@ -200,6 +216,7 @@ class ViTHip(ExplicitBackward, nn.Module):
         self.comm_reserve_cus = 0  # data-parallel runs: CUs the backward's GEMM grids leave to RCCL (see ConvNeXtHip)
         self.comm_cu_mask = False
         self.wgrad_target = int(os.environ.get("SV_VIT_WGRAD_WGS", "256"))
+        self._register_load_state_dict_pre_hook(self._resample_pos_embed_hook)
         self._init_weights()
 
     # -- timm init: trunc_normal(.02) for pos_embed and the Linears, zero Linear biases, normal(1e-6) class token; the
@@ -211,6 +228,28 @@ class ViTHip(ExplicitBackward, nn.Module):
             if isinstance(m, nn.Linear):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 nn.init.zeros_(m.bias)
+
+    def _resample_pos_embed_hook(self, state_dict, prefix, *args) -> None:
+        """Weights trained at another (square) image size: ``pos_embed`` is resampled to this model's grid, as timm's
+        checkpoint filter does.  Anything else that does not fit stays the error load_state_dict reports."""
+        key = prefix + "pos_embed"
+        pe = state_dict.get(key)
+        if not isinstance(pe, torch.Tensor) or pe.dim() != 3 or pe.shape[0] != 1 or pe.shape[2] != self.dim \
+                or pe.shape[1] == self.pos_embed.shape[1]:
+            return
+        npt = 0 if self.no_embed_class else 1
+        g = math.isqrt(max(pe.shape[1] - npt, 0))
+        if g == 0 or g * g != pe.shape[1] - npt:
+            return  # not a square grid: the shape mismatch is reported by load_state_dict
+        new = self.img_size // PATCH
+        state_dict[key] = resample_abs_pos_embed(pe, (new, new), npt)
+        global _RESAMPLE_LOGGED
+        if not _RESAMPLE_LOGGED:
+            _RESAMPLE_LOGGED = True
+            _log.info("resampled %s from a %dx%d to a %dx%d grid (bicubic, antialias)", key, g, g, new, new)
+
+    def _use_stream(self) -> bool:
+        return self.attn_stream or self.num_tokens > K.ATTN_MAX_N
 
     # -- precision / weight shadows --------------------------------------------------------------
     @property
@@ -277,7 +316,8 @@ class ViTHip(ExplicitBackward, nn.Module):
         y1, m1, r1 = K.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, out_dtype=act)
         qkv = torch.empty(M, 3 * C, device=x.device, dtype=act)
         K.linear_fwd(y1, self._w(blk.attn.qkv.weight, cache), out=qkv, bias=blk.attn.qkv.bias, compute_bf16=bf)
-        o, lse = K.attn_fwd(qkv, B, N, self.heads, img_rows=Np)
+        attn_fwd = K.attn_stream_fwd if self._use_stream() else K.attn_fwd
+        o, lse = attn_fwd(qkv, B, N, self.heads, img_rows=Np)
         x1 = torch.empty(M, C, device=x.device, dtype=torch.float32)
         K.linear_fwd(o, self._w(blk.attn.proj.weight, cache), out=x1, bias=blk.attn.proj.bias, gamma=self._gamma(blk.ls1),
                      residual=x, epilogue=nv.SV_EPI_BIAS_GAMMA_RES, compute_bf16=bf)
@@ -373,7 +413,8 @@ class ViTHip(ExplicitBackward, nn.Module):
         dsrc = K.cast_bf16(d) if bf else d
         do = torch.empty(M, C, device=d.device, dtype=act)
         self._res_branch_backward(blk.attn.proj, blk.ls1, o, dsrc, do, wg, cache)
-        dqkv = K.attn_bwd(qkv, o, lse, do, B, N, self.heads, img_rows=Np)
+        attn_bwd = K.attn_stream_bwd if self._use_stream() else K.attn_bwd
+        dqkv = attn_bwd(qkv, o, lse, do, B, N, self.heads, img_rows=Np)
         dy1 = torch.empty(M, C, device=d.device, dtype=torch.float32)
         K.linear_dgrad(dqkv, self._w(aq.weight, cache), out=dy1, compute_bf16=bf, policy=wg.pol)
         K.layernorm_bwd(dy1, x, m1, r1, blk.norm1.weight, dw=g(blk.norm1.weight), db=g(blk.norm1.bias), dx=d,
@@ -424,8 +465,33 @@ class ViTHip(ExplicitBackward, nn.Module):
         self._ready([self.cls_token, self.pos_embed, proj.weight, proj.bias])
 
 
-def create_vit(name: str, precision: str = "bf16", img_size: int = 224) -> ViTHip:
+def resample_abs_pos_embed(posemb: torch.Tensor, new_grid, num_prefix_tokens: int = 1) -> torch.Tensor:
+    """A [1, prefix + g * g, C] absolute position embedding on another grid (timm 1.0.22 ``resample_abs_pos_embed``
+    as published): the prefix tokens are copied, the grid part is interpolated in float as a [1, C, g, g] image
+    (bicubic, antialias, align_corners=False) and cast back."""
+    new_h, new_w = (new_grid, new_grid) if isinstance(new_grid, int) else new_grid
+    prefix, grid = posemb[:, :num_prefix_tokens], posemb[:, num_prefix_tokens:]
+    g = math.isqrt(grid.shape[1])
+    if g * g != grid.shape[1]:
+        raise ValueError(f"position embedding of {grid.shape[1]} grid tokens is not square")
+    if (g, g) == (new_h, new_w):
+        return posemb
+    C = posemb.shape[-1]
+    img = grid.reshape(1, g, g, C).permute(0, 3, 1, 2).float()
+    img = F.interpolate(img, size=(new_h, new_w), mode="bicubic", antialias=True, align_corners=False)
+    grid = img.permute(0, 2, 3, 1).reshape(1, new_h * new_w, C).to(posemb.dtype)
+    return torch.cat([prefix, grid], dim=1) if num_prefix_tokens else grid
+
+
+def default_img_size() -> int:
+    """The image size of a ViT / DeiT-III built without one: env SV_VIT_IMG_SIZE, else 224."""
+    return int(os.environ.get("SV_VIT_IMG_SIZE", "224"))
+
+
+def create_vit(name: str, precision: str = "bf16", img_size=None) -> ViTHip:
     key = name.split(".")[0]
+    if img_size is None:
+        img_size = default_img_size()
     if key not in VIT_CFGS:
         raise ValueError(f"unsupported ViT / DeiT-III variant {name!r}")
     dim, depth, heads, ls_init, no_embed_class = VIT_CFGS[key]

@@ -31,54 +31,17 @@
 //
 // Bounds: every global row access is guarded by row < N (zero fragment otherwise); LDS images are zero-filled up to
 // the 32-row tile boundary and only read below it.
-#include "common.h"
+#include "attn_common.h"
 
 namespace sv {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kD = 64;            // head dimension
 constexpr int kMaxN = 256;        // tokens per image
 constexpr int kLdT = kMaxN + 8;   // row length (elements) of a transposed [d][token] LDS image: 528 B, 8-B aligned
 constexpr int kFwdThreads = 256, kBwdThreads = 512;
 constexpr int kImgElems = kD * kLdT;
 constexpr int kBwdLds = 3 * kImgElems * 2 + 2 * kMaxN * 4;
-constexpr float kLog2e = 1.4426950408889634f;
 
-__device__ __forceinline__ f32x16 mfma(uint4 a, uint4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-// row of accumulator register i in lane half h of a 32x32 tile
-__device__ __forceinline__ int arow(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-// the four k-step fragments (d = 16 s + 8 h .. + 7) of one 64-wide row; `row` = nullptr: zeros
-__device__ __forceinline__ void load_row(const uint16_t* row, int h, uint4 (&f)[4]) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-    f[s] = row ? *reinterpret_cast<const uint4*>(row + 16 * s + 8 * h) : make_uint4(0u, 0u, 0u, 0u);
-}
-// registers 8 s .. 8 s + 7 of an accumulator tile as the bf16 fragment of k-step s of the next MFMA (element j is
-// tile row 16 s + 8 (j >> 2) + 4 h + (j & 3))
-__device__ __forceinline__ uint4 acc_frag(const f32x16& x, int s) {
-  return make_uint4(pack2bf(x[8 * s], x[8 * s + 1]), pack2bf(x[8 * s + 2], x[8 * s + 3]),
-                    pack2bf(x[8 * s + 4], x[8 * s + 5]), pack2bf(x[8 * s + 6], x[8 * s + 7]));
-}
-// the matching fragment of the OTHER operand from a transposed image: row `r` of the image, tokens
-// t0 + 16 s + 4 h + {0..3} and t0 + 16 s + 8 + 4 h + {0..3}
-__device__ __forceinline__ uint4 tr_frag(const uint16_t* img, int r, int t0, int s, int h) {
-  const uint16_t* p = img + r * kLdT + t0 + 16 * s + 4 * h;
-  const uint2 lo = *reinterpret_cast<const uint2*>(p);
-  const uint2 hi = *reinterpret_cast<const uint2*>(p + 8);
-  return make_uint4(lo.x, lo.y, hi.x, hi.y);
-}
 // rows [0, np) of a [rows][ld] bf16 matrix (64 columns from `src`) into a transposed image; rows >= n are zeros
 __device__ __forceinline__ void fill_transposed(uint16_t* img, const uint16_t* src, int64_t ld, int n, int np,
                                                 int tid, int nthreads) {
@@ -93,21 +56,6 @@ __device__ __forceinline__ void fill_transposed(uint16_t* img, const uint16_t* s
       img[(c * 8 + 2 * j + 1) * kLdT + t] = (uint16_t)(w[j] >> 16);
     }
   }
-}
-// 64 columns of rows [n, rows) of a [rows][ld] bf16 matrix := 0
-__device__ __forceinline__ void zero_pad_rows(uint16_t* dst, int64_t ld, int n, int rows, int tid, int nthreads) {
-  for (int idx = tid; idx < (rows - n) * 8; idx += nthreads)
-    *reinterpret_cast<uint4*>(dst + (int64_t)(n + (idx >> 3)) * ld + (idx & 7) * 8) = make_uint4(0u, 0u, 0u, 0u);
-}
-// a 64 (d) x 32 (token on the lane) pair of accumulator tiles -> rows of a [token][ld] bf16 matrix
-__device__ __forceinline__ void store_t(uint16_t* row, const f32x16 (&acc)[2], float mul, int h) {
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<uint2*>(row + dt * 32 + 8 * g + 4 * h) =
-          make_uint2(pack2bf(acc[dt][4 * g] * mul, acc[dt][4 * g + 1] * mul),
-                     pack2bf(acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul));
 }
 
 __global__ void __launch_bounds__(kFwdThreads) attn_fwd_kernel(const uint16_t* __restrict__ qkv,
@@ -173,7 +121,7 @@ __global__ void __launch_bounds__(kFwdThreads) attn_fwd_kernel(const uint16_t* _
       for (int s = 0; s < 2; ++s) {
         const uint4 pf = acc_frag(S[kt], s);
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) O[dt] = mfma(tr_frag(Vt, dt * 32 + r, kt * 32, s, h), pf, O[dt]);
+        for (int dt = 0; dt < 2; ++dt) O[dt] = mfma(tr_frag(Vt, kLdT, dt * 32 + r, kt * 32, s, h), pf, O[dt]);
       }
   if (qv) store_t(ob + (int64_t)q * C, O, 1.0f / l, h);
 }
@@ -262,8 +210,8 @@ __global__ void __launch_bounds__(kBwdThreads) attn_bwd_kernel(const uint16_t* _
         const uint4 pf = acc_frag(S, s), dsf = acc_frag(dP, s);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          dVt[dt] = mfma(tr_frag(dOt, dt * 32 + r, qt * 32, s, h), pf, dVt[dt]);
-          dKt[dt] = mfma(tr_frag(Qt, dt * 32 + r, qt * 32, s, h), dsf, dKt[dt]);
+          dVt[dt] = mfma(tr_frag(dOt, kLdT, dt * 32 + r, qt * 32, s, h), pf, dVt[dt]);
+          dKt[dt] = mfma(tr_frag(Qt, kLdT, dt * 32 + r, qt * 32, s, h), dsf, dKt[dt]);
         }
       }
     }
@@ -297,14 +245,12 @@ __global__ void __launch_bounds__(kBwdThreads) attn_bwd_kernel(const uint16_t* _
       for (int s = 0; s < 2; ++s) {
         const uint4 dsf = acc_frag(dP, s);
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) dQt[dt] = mfma(tr_frag(Kt, dt * 32 + r, kt * 32, s, h), dsf, dQt[dt]);
+        for (int dt = 0; dt < 2; ++dt) dQt[dt] = mfma(tr_frag(Kt, kLdT, dt * 32 + r, kt * 32, s, h), dsf, dQt[dt]);
       }
     }
     if (ownv) store_t(dqb + (int64_t)own * ld, dQt, 1.0f, h);
   }
 }
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // argument checks shared by the two passes; SV_OK, or the status already reported through set_error
 static int check_args(const char* who, int B, int N, int64_t img_rows, int heads, int head_dim, float scale) {

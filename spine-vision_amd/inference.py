@@ -13,6 +13,7 @@ ImageNet Normalize.  The batched form does the Normalize on the GPU (the stem's 
 
 from __future__ import annotations
 
+import math
 from pathlib import Path
 
 import numpy as np
@@ -36,19 +37,36 @@ def normalize_to_uint8(arr: np.ndarray) -> np.ndarray:
 
 
 def _backbone_name(variant: str) -> str:
-    # cropping.py:424-428; a full registry name of another family ("vit_base", "deit_small": 224x224 images only)
-    # passes through
+    # cropping.py:424-428; a full registry name of another family ("vit_base", "deit_small": built at the image size
+    # the checkpoint's position embedding implies) passes through
     if variant.startswith(("vit_", "deit_")):
         return variant
     return f"convnext_{variant}" if not variant.startswith("v2_") else f"convnextv2_{variant[3:]}"
+
+
+def _vit_img_size(name: str, state: dict) -> int | None:
+    """The image size a ViT / DeiT-III checkpoint was trained at, from the rows of its ``backbone.pos_embed`` (the
+    patch grid, after the class-token row where the embedding has one); None for every other family."""
+    pe = state.get("backbone.pos_embed")
+    if pe is None or not name.startswith(("vit_", "deit_")):
+        return None
+    from .backbone.vit import PATCH, VIT_CFGS
+
+    grid = pe.shape[1] - (0 if VIT_CFGS[name][4] else 1)
+    g = math.isqrt(max(grid, 0))
+    if g == 0 or g * g != grid:
+        raise ValueError(f"backbone.pos_embed has {pe.shape[1]} rows: not a square patch grid for {name}")
+    return g * PATCH
 
 
 def load_localization_model(model_path: Path, variant: str, device: str, precision: str | None = None) -> torch.nn.Module:
     """CoordinateRegressor(convnext_<variant>, 5 levels) with the checkpoint's ``model_state_dict``, on
     ``device``, in eval mode (cropping.py:407-440).  ``precision``: the HIP backbone's compute mode
     (None = the default bf16; "fp32" = the parity mode)."""
-    model = CoordinateRegressor(backbone=_backbone_name(variant), pretrained=False, num_levels=5, precision=precision)
     ck = torch.load(Path(model_path), map_location="cpu", weights_only=True)
+    name = _backbone_name(variant)
+    model = CoordinateRegressor(backbone=name, pretrained=False, num_levels=5, precision=precision,
+                                img_size=_vit_img_size(name, ck["model_state_dict"]))
     model.load_state_dict(ck["model_state_dict"])
     model.to(device)
     model.eval()

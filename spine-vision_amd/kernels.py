@@ -638,7 +638,7 @@ def layernorm_bwd(dy2d, x2d, mean, rstd, w, *, dw, db, dx=None, accumulate_dx=Fa
 
 
 # ----------------------------------------------------------------------------------------------
-# Multi-head self-attention (ViT / DeiT-III, csrc/attn.hip)
+# Multi-head self-attention (ViT / DeiT-III, csrc/attn.hip; above 256 tokens csrc/attn_stream.hip)
 # SV_ATTN=torch: the same maths as torch ops on views of the same buffers (A/B and parity arm, in the style of
 # SV_GCONV=dense): matmul -> f32 softmax -> bf16 -> matmul, and an explicit backward from the same formulas (no
 # autograd).  The two products that feed f32 maths (q k^T and dout v^T) take f32 copies of the bf16 operands, so they
@@ -646,7 +646,8 @@ def layernorm_bwd(dy2d, x2d, mean, rstd, w, *, dw, db, dx=None, accumulate_dx=Fa
 # the fp32 parity mode that does not run on this library.
 ATTN_TORCH = os.environ.get("SV_ATTN", "") == "torch"
 ATTN_HEAD_DIM = 64
-ATTN_MAX_N = 256
+ATTN_MAX_N = 256  # sv_attn_fwd / sv_attn_bwd: every key of a head in one pass
+ATTN_STREAM_MAX_N = 2048  # sv_attn_stream_fwd / sv_attn_stream_bwd
 
 
 def _attn_geometry(who: str, qkv, B: int, N: int, heads: int, img_rows) -> tuple[int, int]:
@@ -670,19 +671,20 @@ def _attn_torch_arm(qkv) -> bool:
 
 
 def attn_fwd(qkv, B: int, N: int, heads: int, *, img_rows: int | None = None, scale: float | None = None,
-             out: torch.Tensor | None = None, lse: torch.Tensor | None = None, torch_arm: bool | None = None):
+             out: torch.Tensor | None = None, lse: torch.Tensor | None = None, torch_arm: bool | None = None,
+             _who: str = "attn_fwd", _max_n: int = ATTN_MAX_N):
     """(out [B * img_rows, heads * 64], lse f32 [B, heads, N]) = softmax(q k^T * scale) v per (image, head) of
     qkv [B * img_rows, 3 * heads * 64] (columns (q|k|v, head, d); an image's first N rows are its tokens, the other
     rows padding: not read, zero in ``out``).  bf16 operands run sv_attn_fwd unless ``torch_arm`` (default: the
     SV_ATTN=torch switch); f32 operands always run the torch arm in f32."""
-    rows, C = _attn_geometry("attn_fwd", qkv, B, N, heads, img_rows)
+    rows, C = _attn_geometry(_who, qkv, B, N, heads, img_rows)
     scale = ATTN_HEAD_DIM ** -0.5 if scale is None else float(scale)
     if out is None:
         out = torch.empty(B * rows, C, device=qkv.device, dtype=qkv.dtype)
     if lse is None:
         lse = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32)
-    _check(tuple(out.shape) == (B * rows, C) and out.is_contiguous() and out.dtype == qkv.dtype, "attn_fwd: bad out")
-    _check(tuple(lse.shape) == (B, heads, N) and lse.is_contiguous() and lse.dtype == torch.float32, "attn_fwd: bad lse")
+    _check(tuple(out.shape) == (B * rows, C) and out.is_contiguous() and out.dtype == qkv.dtype, f"{_who}: bad out")
+    _check(tuple(lse.shape) == (B, heads, N) and lse.is_contiguous() and lse.dtype == torch.float32, f"{_who}: bad lse")
     if _attn_torch_arm(qkv) if torch_arm is None else (torch_arm or qkv.dtype == torch.float32):
         q, k, v = _attn_views(qkv, B, rows, N, heads, 3)
         s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
@@ -693,23 +695,32 @@ def attn_fwd(qkv, B: int, N: int, heads: int, *, img_rows: int | None = None, sc
         if rows > N:
             o[:, N:] = 0
         return out, lse
-    _check(N <= ATTN_MAX_N, f"attn_fwd: N = {N} tokens (at most {ATTN_MAX_N})")
-    call("sv_attn_fwd", ptr(qkv), ptr(out), ptr(lse), B, N, rows, heads, ATTN_HEAD_DIM, scale)
+    _check(N <= _max_n, f"{_who}: N = {N} tokens (at most {_max_n})")
+    call("sv_" + _who, ptr(qkv), ptr(out), ptr(lse), B, N, rows, heads, ATTN_HEAD_DIM, scale)
     return out, lse
 
 
+def attn_stream_fwd(qkv, B: int, N: int, heads: int, *, img_rows: int | None = None, scale: float | None = None,
+                    out: torch.Tensor | None = None, lse: torch.Tensor | None = None, torch_arm: bool | None = None):
+    """``attn_fwd`` for N up to ATTN_STREAM_MAX_N: bf16 operands run sv_attn_stream_fwd (K and V streamed through LDS
+    in tiles, online softmax); the torch arm is attn_fwd's, which takes any N."""
+    return attn_fwd(qkv, B, N, heads, img_rows=img_rows, scale=scale, out=out, lse=lse, torch_arm=torch_arm,
+                    _who="attn_stream_fwd", _max_n=ATTN_STREAM_MAX_N)
+
+
 def attn_bwd(qkv, out, lse, dout, B: int, N: int, heads: int, *, img_rows: int | None = None,
-             scale: float | None = None, dqkv: torch.Tensor | None = None, torch_arm: bool | None = None):
+             scale: float | None = None, dqkv: torch.Tensor | None = None, torch_arm: bool | None = None,
+             _who: str = "attn_bwd", _max_n: int = ATTN_MAX_N):
     """dqkv [B * img_rows, 3 * heads * 64] from dout [B * img_rows, heads * 64]: P recomputed from ``lse``,
     D = rowsum(dout . out), dv = P^T dout, dS = P (dout v^T - D) scale, dq = dS k, dk = dS^T q (pad rows zero)."""
-    rows, C = _attn_geometry("attn_bwd", qkv, B, N, heads, img_rows)
+    rows, C = _attn_geometry(_who, qkv, B, N, heads, img_rows)
     scale = ATTN_HEAD_DIM ** -0.5 if scale is None else float(scale)
     for name, t_ in (("out", out), ("dout", dout)):
-        _check(tuple(t_.shape) == (B * rows, C) and t_.is_contiguous() and t_.dtype == qkv.dtype, f"attn_bwd: bad {name}")
-    _check(tuple(lse.shape) == (B, heads, N) and lse.is_contiguous() and lse.dtype == torch.float32, "attn_bwd: bad lse")
+        _check(tuple(t_.shape) == (B * rows, C) and t_.is_contiguous() and t_.dtype == qkv.dtype, f"{_who}: bad {name}")
+    _check(tuple(lse.shape) == (B, heads, N) and lse.is_contiguous() and lse.dtype == torch.float32, f"{_who}: bad lse")
     if dqkv is None:
         dqkv = torch.empty_like(qkv)
-    _check(dqkv.shape == qkv.shape and dqkv.is_contiguous() and dqkv.dtype == qkv.dtype, "attn_bwd: bad dqkv")
+    _check(dqkv.shape == qkv.shape and dqkv.is_contiguous() and dqkv.dtype == qkv.dtype, f"{_who}: bad dqkv")
     if _attn_torch_arm(qkv) if torch_arm is None else (torch_arm or qkv.dtype == torch.float32):
         q, k, v = _attn_views(qkv, B, rows, N, heads, 3)
         (o,), (do,) = _attn_views(out, B, rows, N, heads, 1), _attn_views(dout, B, rows, N, heads, 1)
@@ -724,9 +735,22 @@ def attn_bwd(qkv, out, lse, dout, B: int, N: int, heads: int, *, img_rows: int |
         if rows > N:
             g[:, N:] = 0
         return dqkv
-    _check(N <= ATTN_MAX_N, f"attn_bwd: N = {N} tokens (at most {ATTN_MAX_N})")
-    call("sv_attn_bwd", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), B, N, rows, heads, ATTN_HEAD_DIM, scale)
+    _check(N <= _max_n, f"{_who}: N = {N} tokens (at most {_max_n})")
+    if _who == "attn_bwd":
+        call("sv_attn_bwd", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), B, N, rows, heads, ATTN_HEAD_DIM, scale)
+    else:  # the streaming pair: D = rowsum(dout . out) goes through a workspace the library does not allocate
+        dws = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32)
+        call("sv_attn_stream_bwd", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), ptr(dws), B, N, rows, heads,
+             ATTN_HEAD_DIM, scale)
     return dqkv
+
+
+def attn_stream_bwd(qkv, out, lse, dout, B: int, N: int, heads: int, *, img_rows: int | None = None,
+                    scale: float | None = None, dqkv: torch.Tensor | None = None, torch_arm: bool | None = None):
+    """``attn_bwd`` for N up to ATTN_STREAM_MAX_N on sv_attn_stream_bwd (a D pre-pass, a dk / dv kernel and a dq
+    kernel, no atomics); the torch arm is attn_bwd's."""
+    return attn_bwd(qkv, out, lse, dout, B, N, heads, img_rows=img_rows, scale=scale, dqkv=dqkv, torch_arm=torch_arm,
+                    _who="attn_stream_bwd", _max_n=ATTN_STREAM_MAX_N)
 
 
 def patchify16(img, *, out_dtype, rows_per_img: int | None = None, row0: int = 0, out: torch.Tensor | None = None,

@@ -207,6 +207,8 @@ _SIGS = {
     # ViT / DeiT-III
     "sv_attn_fwd": [_p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
     "sv_attn_bwd": [_p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
+    "sv_attn_stream_fwd": [_p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
+    "sv_attn_stream_bwd": [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
     "sv_patchify16": [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i64, _i32, _p],
     "sv_vit_tokens": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_image_to_nhwc": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],

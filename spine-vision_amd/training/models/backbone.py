@@ -7,7 +7,9 @@ for the backbones on the north-star path -- ConvNeXt-tiny/small/base/large and C
 (localization) and the ResNet family (classification): ResNet-18/34/50/101/152, the ``resnet50_a2`` / ``_b`` /
 ``_c`` recipes of ResNet-50, Wide-ResNet-50/101 and ResNeXt-50 (32x4d, its grouped 3x3 on csrc/gconv.hip) -- and
 the plain transformers: ViT-tiny/small/base/large (patch 16) and DeiT-III small/base (``deit_tiny`` is the
-reference's alias of deit3_small), their attention on csrc/attn.hip; these take 224x224 images only.  Every
+reference's alias of deit3_small), their attention on csrc/attn.hip (up to 256 tokens) and csrc/attn_stream.hip (up to 2048); these are
+strict about the image size: one square ``img_size``, a multiple of 16 up to 2048 tokens (224, 256, 384, 512, ...),
+given to ``create`` / ``Classifier`` / ``CoordinateRegressor`` or through env ``SV_VIT_IMG_SIZE`` (default 224).  Every
 other name of the reference registry is recognised (``list_backbones`` returns the reference's full list) but
 raises: those families (Swin, EfficientNet, MobileNet; and ConvNeXt-xlarge, the other ConvNeXt V2 sizes,
 ``resnext101``, ``resnet50_d`` and ``resnetrs*``) are outside this build's scope.
@@ -74,7 +76,10 @@ class BackboneFactory:
     precision: str = "bf16"  # default compute precision of created backbones ("bf16" | "fp32")
 
     @classmethod
-    def create(cls, name: str, pretrained: bool = True, precision: str | None = None) -> tuple[nn.Module, int]:
+    def create(cls, name: str, pretrained: bool = True, precision: str | None = None,
+               img_size=None) -> tuple[nn.Module, int]:
+        """``img_size`` (an int or a square pair) sizes a ViT / DeiT-III backbone, which is strict about its input
+        size (None: env SV_VIT_IMG_SIZE, else 224); every other family takes any size and ignores it."""
         if name not in BACKBONES:
             raise ValueError(f"Unknown backbone: {name}. Available: {', '.join(sorted(BACKBONES))}")
         if name not in NATIVE:
@@ -89,7 +94,7 @@ class BackboneFactory:
         elif name.startswith(("vit_", "deit_")):
             from ...backbone.vit import create_vit
 
-            model = create_vit(name, precision=prec)
+            model = create_vit(name, precision=prec, img_size=img_size)
         else:
             from ...backbone.resnet import create_resnet
 

@@ -90,12 +90,14 @@ class _FusedHeadLoss(torch.autograd.Function):
 
 class Classifier(BaseModel):
     def __init__(self, backbone: str = "resnet50", tasks: list[TaskConfig] | None = None, pretrained: bool = True,
-                 dropout: float = 0.3, freeze_backbone: bool = False, precision: str | None = None) -> None:
+                 dropout: float = 0.3, freeze_backbone: bool = False, precision: str | None = None,
+                 img_size=None) -> None:
         super().__init__()
         self._backbone_name = backbone
         self._tasks = tasks if tasks is not None else get_tasks()
         self._task_names = [t.name for t in self._tasks]
-        self.backbone, self._feature_dim = BackboneFactory.create(backbone, pretrained, precision=precision)
+        self.backbone, self._feature_dim = BackboneFactory.create(backbone, pretrained, precision=precision,
+                                                                       img_size=img_size)
         self.dropout = nn.Dropout(dropout)
         self.heads = nn.ModuleDict({t.name: nn.Linear(self._feature_dim, t.num_classes) for t in self._tasks})
         self._loss_functions, self._loss_weights = create_loss_functions(self._tasks)
@@ -198,14 +200,15 @@ class CoordinateRegressor(BaseModel):
     def __init__(self, backbone: str = "convnext_base", num_outputs: int = 2, pretrained: bool = True,
                  dropout: float = 0.2, freeze_backbone: bool = False, head_config: Any = None,
                  num_levels: int = 5, loss_type: Literal["mse", "smooth_l1", "huber"] = "smooth_l1",
-                 precision: str | None = None) -> None:
+                 precision: str | None = None, img_size=None) -> None:
         super().__init__()
         if head_config is not None:
             raise NotImplementedError("custom head_config is outside the MI355X training path (default head only)")
         self._backbone_name = backbone
         self._num_outputs, self._num_levels = num_outputs, num_levels
         self._loss_type = loss_type
-        self.backbone, self._feature_dim = BackboneFactory.create(backbone, pretrained, precision=precision)
+        self.backbone, self._feature_dim = BackboneFactory.create(backbone, pretrained, precision=precision,
+                                                                       img_size=img_size)
         self.head = nn.Sequential(
             nn.LayerNorm(self._feature_dim),
             nn.Dropout(dropout),

@@ -89,7 +89,7 @@ class ClassificationTrainer(BaseTrainer):
         if model is None:
             model = Classifier(backbone=config.backbone, tasks=tasks, pretrained=config.pretrained,
                                dropout=config.dropout, freeze_backbone=config.freeze_backbone_epochs > 0,
-                               precision=config.effective_precision)
+                               precision=config.effective_precision, img_size=tuple(config.output_size))
         super().__init__(config, model, train_dataset, val_dataset)
         self._target_labels = target_labels
         self._tasks = tasks

@@ -52,7 +52,7 @@ class LocalizationTrainer(BaseTrainer):
             model = CoordinateRegressor(backbone=config.backbone, num_outputs=2, pretrained=config.pretrained,
                                         dropout=config.dropout, freeze_backbone=config.freeze_backbone_epochs > 0,
                                         num_levels=config.num_levels, loss_type=config.loss_type,
-                                        precision=config.effective_precision)
+                                        precision=config.effective_precision, img_size=tuple(config.image_size))
         if train_dataset is None:
             train_dataset = LocalizationDataset(Path(config.data_path), split="train", val_ratio=config.val_split,
                                                 series_types=config.series_types, sources=config.sources,

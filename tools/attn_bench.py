@@ -1,9 +1,13 @@
-"""Standalone timing of the fused attention kernels (csrc/attn.hip) against the SV_ATTN=torch arm (the same maths as
+"""Standalone timing of the fused attention kernels (csrc/attn.hip; --arm stream: csrc/attn_stream.hip) against the SV_ATTN=torch arm (the same maths as
 torch matmul / softmax ops on views of the same buffers) at the ViT shapes: N = 197 tokens in the module's 200-row
 layout, batch 32, heads 3 / 6 / 12 / 16 (vit_tiny / small / base / large).  HIP events; per shape and pass the arms
 alternate, and the whole table runs --rounds times.
 
     python tools/attn_bench.py [--iters 30] [--rounds 2] [--batch 32] [--heads 3,6,12,16] [--tokens 197]
+    python tools/attn_bench.py --arm stream --tokens 197,257,577,1025      # 224 / 256 / 384 / 512 px
+
+--arm stream times the streaming pair as the HIP column at every token count (at most 2048); where the one-pass
+kernels also run (N <= 256) they are one more column (``onepass_us``), alternated with the others, not part of the bar.
 
 One JSON line per (round, heads, pass).  Bytes are algorithmic (forward: qkv read, out and lse written; backward: qkv,
 out, dout, lse read, dqkv written) against the 6.3 TB/s an HBM-bound kernel reaches on the MI355X; FLOPs are the
@@ -76,7 +80,9 @@ def _sdpa_arms(sets, B, N, rows, heads):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--heads", default="3,6,12,16")
-    ap.add_argument("--tokens", type=int, default=197)
+    ap.add_argument("--tokens", default="197", help="comma-separated token counts N")
+    ap.add_argument("--arm", choices=("onepass", "stream"), default="onepass",
+                    help="the HIP column: the one-pass kernels (N <= 256) or the streaming pair (N <= 2048)")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32)
@@ -85,40 +91,45 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("attn_bench needs a GPU")
     dev = torch.device("cuda:0")
-    B, N = args.batch, args.tokens
-    rows = -(-N // 8) * 8
+    B = args.batch
+    stream = args.arm == "stream"
+    hip_fwd, hip_bwd = (K.attn_stream_fwd, K.attn_stream_bwd) if stream else (K.attn_fwd, K.attn_bwd)
     bf = torch.bfloat16
     worst = {}
+    shapes = [(int(h), int(n)) for n in args.tokens.split(",") for h in args.heads.split(",")]
     for rnd in range(args.rounds):
-        for heads in (int(h) for h in args.heads.split(",")):
+        for heads, N in shapes:
+            rows = -(-N // 8) * 8
             C = heads * 64
             sets = []
             for _ in range(args.ring):
                 qkv = (torch.rand(B * rows, 3 * C, device=dev) * 2 - 1).to(bf)
                 dout = (torch.rand(B * rows, C, device=dev) * 2 - 1).to(bf)
-                out, lse = K.attn_fwd(qkv, B, N, heads, img_rows=rows, torch_arm=False)
+                out, lse = hip_fwd(qkv, B, N, heads, img_rows=rows, torch_arm=False)
                 sets.append((qkv, dout, out, lse, torch.empty_like(out), torch.empty_like(lse), torch.empty_like(qkv)))
             tok = B * N
             nbytes = {"fwd": 2.0 * tok * 4 * C + 4.0 * tok * heads, "bwd": 2.0 * tok * 8 * C + 4.0 * tok * heads}
             flops = {"fwd": 4.0 * B * heads * N * N * 64, "bwd": 10.0 * B * heads * N * N * 64}
 
-            def arms(torch_arm):
+            def arms(fwd, bwd, torch_arm):
                 return {
-                    "fwd": [lambda s=s: K.attn_fwd(s[0], B, N, heads, img_rows=rows, out=s[4], lse=s[5],
-                                                   torch_arm=torch_arm) for s in sets],
-                    "bwd": [lambda s=s: K.attn_bwd(s[0], s[2], s[3], s[1], B, N, heads, img_rows=rows, dqkv=s[6],
-                                                   torch_arm=torch_arm) for s in sets],
+                    "fwd": [lambda s=s: fwd(s[0], B, N, heads, img_rows=rows, out=s[4], lse=s[5], torch_arm=torch_arm)
+                            for s in sets],
+                    "bwd": [lambda s=s: bwd(s[0], s[2], s[3], s[1], B, N, heads, img_rows=rows, dqkv=s[6],
+                                            torch_arm=torch_arm) for s in sets],
                 }
 
-            hip, tor = arms(False), arms(True)
+            cols = {"hip": arms(hip_fwd, hip_bwd, False), "torch": arms(hip_fwd, hip_bwd, True)}
+            if stream and N <= K.ATTN_MAX_N:
+                cols["onepass"] = arms(K.attn_fwd, K.attn_bwd, False)
             sd = _sdpa_arms(sets, B, N, rows, heads)
             for i, pname in enumerate(("fwd", "bwd")):
-                t = {"hip": [], "torch": []}
+                t = {c: [] for c in cols}
                 for _ in range(2):  # the arms alternate
-                    t["hip"].append(timeit(hip[pname], args.iters))
-                    t["torch"].append(timeit(tor[pname], args.iters))
+                    for c in cols:
+                        t[c].append(timeit(cols[c][pname], args.iters))
                 hus, tus = min(t["hip"]), min(t["torch"])
-                rec = {"round": rnd, "B": B, "N": N, "img_rows": rows, "heads": heads, "pass": pname,
+                rec = {"round": rnd, "arm": args.arm, "B": B, "N": N, "img_rows": rows, "heads": heads, "pass": pname,
                        "hip_us": round(hus, 2), "torch_us": round(tus, 2), "hip_us_all": [round(v, 2) for v in t["hip"]],
                        "torch_us_all": [round(v, 2) for v in t["torch"]], "speedup": round(tus / hus, 2),
                        "algorithmic_MB": round(nbytes[pname] / 1e6, 2), "hip_TBs": round(nbytes[pname] / hus / 1e6, 3),
@@ -126,15 +137,19 @@ def main():
                        "GFLOP": round(flops[pname] / 1e9, 2), "hip_TFs": round(flops[pname] / hus / 1e6, 1),
                        "share_of_bf16_peak": round(flops[pname] / hus / 1e6 / BF16_PEAK_TFS, 4),
                        "hip_faster": bool(hus < tus)}
+                if "onepass" in t:
+                    rec["onepass_us"] = round(min(t["onepass"]), 2)
+                    rec["onepass_us_all"] = [round(v, 2) for v in t["onepass"]]
                 if sd is not None:
                     rec["sdpa_us"] = round(timeit(sd[i], args.iters), 2)
-                worst[(heads, pname)] = worst.get((heads, pname), True) and rec["hip_faster"]
+                if not stream or N > K.ATTN_MAX_N:  # the streaming pair's bar is set above the one-pass kernels' range
+                    worst[(heads, N, pname)] = worst.get((heads, N, pname), True) and rec["hip_faster"]
                 print(json.dumps(rec), flush=True)
-            del sets, hip, tor, sd
+            del sets, cols, sd
             torch.cuda.empty_cache()
     lost = sorted(k for k, v in worst.items() if not v)
     print(json.dumps({"bar": "the HIP kernel faster than the torch arm on every shape and pass in every round",
-                      "met": not lost, "lost": [f"heads{a}/{b}" for a, b in lost]}), flush=True)
+                      "met": not lost, "lost": [f"heads{a}/N{n}/{b}" for a, n, b in lost]}), flush=True)
 
 
 if __name__ == "__main__":
