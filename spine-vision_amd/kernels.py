@@ -784,15 +784,17 @@ def patchify16(img, *, out_dtype, rows_per_img: int | None = None, row0: int = 0
 
 
 def vit_tokens(pe: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, B: int, P: int, rows_per_img: int,
-               pos_has_cls: bool) -> torch.Tensor:
+               pos_has_cls: bool, out: torch.Tensor | None = None) -> torch.Tensor:
     """The token matrix [B * rows_per_img, C] f32 (sv_vit_tokens): per image row 0 the class token (+ pos[0] for ViT),
-    rows 1..P the patch embeddings ``pe`` (same row layout) + their position embedding, the rest zero."""
+    rows 1..P the patch embeddings ``pe`` (same row layout) + their position embedding, the rest zero.  ``out``: the
+    buffer to write (default: a fresh one)."""
     C = pe.shape[1]
     _check(tuple(pe.shape) == (B * rows_per_img, C) and pe.dtype == torch.float32 and pe.is_contiguous(),
            "vit_tokens: pe must be contiguous f32 [B * rows_per_img, C]")
     _check(cls.numel() == C and pos.numel() == (P + int(bool(pos_has_cls))) * C and cls.dtype == pos.dtype == torch.float32
            and cls.is_contiguous() and pos.is_contiguous(), "vit_tokens: bad cls / pos")
-    x = torch.empty_like(pe)
+    x = torch.empty_like(pe) if out is None else out
+    _check(x.shape == pe.shape and x.dtype == torch.float32 and x.is_contiguous(), "vit_tokens: bad out")
     call("sv_vit_tokens", ptr(pe), ptr(cls), ptr(pos), ptr(x), B, P, rows_per_img, C, int(bool(pos_has_cls)))
     return x
 

@@ -12,8 +12,14 @@ and D two f32 sums of the same 64 products in different orders (terms below 1.5,
 1e-5, times scale 0.125 and |k|, |q| < 1.5): the bound there is 5e-6 absolute.
 
 Inputs: q, k uniform in [-1.5, 1.5] (scaled scores within about +-4: no softmax row underflows in f32 or f64), v and
-dout uniform in [-1, 1].  Operands and outputs sit inside larger buffers filled with a sentinel; the exact-size views
-are passed and the sentinel elements before and after must be unchanged.
+dout uniform in [-1, 1].  Two more input sets at (1, 2, 129) shift every score of a head by +-98 and leave softmax
+unchanged in exact arithmetic: q[..., 0] = 28 for every query and k[..., 0] = +28 ("shift_up") or -28 ("shift_down")
+for every key, both exact in bf16, so the scaled scores lie in [94, 102] or [-102, -94] and lse is about +-98 + log N:
+a forward without the max subtraction overflows or underflows, a backward that mishandles a large lse loses P.  Same
+checks and bound rule; each own error of these two must stay below 2e-2 (measured on the CPU at N = 65 and 257: out
+2.4e-3, dq 1.2e-2, dk 2.2e-3, dv 2.5e-3), so that the 3 x own bound cannot become vacuous.  The first scaled-score
+line above describes the uniform sets only.  Operands and outputs sit inside larger buffers filled with a sentinel; the
+exact-size views are passed and the sentinel elements before and after must be unchanged.
 
 The ViT module keeps each image's tokens in rows padded to a multiple of 8 (DESIGN.md "ViT / DeiT-III"), so the
 GEMM and LayerNorm row counts stay multiples of 8 as they always were; the padded form of the kernels is checked
@@ -29,7 +35,9 @@ from spine_vision_amd import kernels as K
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 1), (2, 3, 16), (2, 3, 17), (1, 2, 33), (3, 3, 64), (2, 3, 197), (1, 16, 197), (2, 2, 256)]
-IDS = ["x".join(map(str, s)) for s in SHAPES]
+CASES = [(s, "uniform") for s in SHAPES] + [((1, 2, 129), "shift_up"), ((1, 2, 129), "shift_down")]
+IDS = ["x".join(map(str, s)) + ("" if v == "uniform" else "-" + v) for s, v in CASES]
+SHIFT = 28.0  # exact in bf16; 28 * 28 * SCALE = 98
 SCALE = 0.125
 SENTINEL = -7.0  # exactly representable in bf16 and f32
 GUARD = 256  # sentinel elements on either side (keeps the views 16-byte aligned)
@@ -56,14 +64,18 @@ def _rel(a, b):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(shape):
+def _case(case):
     """bf16-rounded qkv / dout (float64 values), the float64 reference and the rounding-only restatement's error;
-    computed once per shape on the CPU, shared by the tests, never modified."""
-    B, heads, N = shape
+    computed once per case on the CPU, shared by the tests, never modified."""
+    (B, heads, N), variant = case
     g = torch.Generator().manual_seed(7919 * B + 131 * heads + N)
     C = heads * 64
     qkv = torch.rand(B * N, 3 * C, generator=g, dtype=torch.float64) * 2 - 1
     qkv.view(B * N, 3, C)[:, :2] *= 1.5
+    if variant != "uniform":
+        qk = qkv.view(B, N, 3, heads, 64)
+        qk[:, :, 0, :, 0] = SHIFT
+        qk[:, :, 1, :, 0] = SHIFT if variant == "shift_up" else -SHIFT
     qkv = _bf(qkv)
     dout = _bf(torch.rand(B * N, C, generator=g, dtype=torch.float64) * 2 - 1)
     x = qkv.clone().requires_grad_(True)
@@ -117,9 +129,9 @@ def _run(dev, qkv, dout, B, N, heads, *, torch_arm=False, img_rows=None):
     return ov, lv, gv
 
 
-def _errors(shape, out, lse, dqkv):
-    B, heads, N = shape
-    c = _case(shape)
+def _errors(case, out, lse, dqkv):
+    (B, heads, N), _ = case
+    c = _case(case)
     ref = c["ref"]
     gq, gk, gv = _split(dqkv.cpu().double(), B, N, heads)
     rq, rk, rv = _split(ref["dqkv"], B, N, heads)
@@ -132,31 +144,33 @@ def _errors(shape, out, lse, dqkv):
     return e
 
 
-def _bound(shape, name):
-    return max(1e-3, 3.0 * _case(shape)["own"][name])
+def _bound(case, name):
+    return max(1e-3, 3.0 * _case(case)["own"][name])
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
-def test_attn_against_float64(dev, shape):
-    B, heads, N = shape
-    c = _case(shape)
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_attn_against_float64(dev, case):
+    (B, heads, N), _ = case
+    c = _case(case)
     out, lse, dqkv = _run(dev, c["qkv"], c["dout"], B, N, heads)
-    e = _errors(shape, out, lse, dqkv)
-    print(f"[attn] {shape}: kernel " + ", ".join(f"{k} {v:.3e}" for k, v in e.items())
+    e = _errors(case, out, lse, dqkv)
+    print(f"[attn] {case}: kernel " + ", ".join(f"{k} {v:.3e}" for k, v in e.items())
           + " | rounding-only restatement " + ", ".join(f"{k} {v:.3e}" for k, v in c["own"].items()))
     assert torch.isfinite(out.float()).all() and torch.isfinite(dqkv.float()).all()
+    if case[1] != "uniform":
+        assert all(v < 2e-2 for v in c["own"].values()), ("the restatement's own error makes the bound vacuous", c["own"])
     for name in ("out", "dq", "dk", "dv"):
         if name in e:
-            assert e[name] <= _bound(shape, name), (name, e[name], _bound(shape, name))
+            assert e[name] <= _bound(case, name), (name, e[name], _bound(case, name))
     if N == 1:
         assert e["dq_abs"] <= 5e-6 and e["dk_abs"] <= 5e-6, e
     assert e["lse_abs"] <= 1e-3, e
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
-def test_attn_bitwise_run_to_run_and_batch_independent(dev, shape):
-    B, heads, N = shape
-    c = _case(shape)
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_attn_bitwise_run_to_run_and_batch_independent(dev, case):
+    (B, heads, N), _ = case
+    c = _case(case)
     a = _run(dev, c["qkv"], c["dout"], B, N, heads)
     b = _run(dev, c["qkv"], c["dout"], B, N, heads)
     for x, y, name in zip(a, b, ("out", "lse", "dqkv")):
@@ -169,14 +183,14 @@ def test_attn_bitwise_run_to_run_and_batch_independent(dev, shape):
     assert torch.equal(one[2], a[2][i * N:(i + 1) * N]), "dqkv depends on the batch"
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
-def test_attn_torch_arm_no_further_from_float64(dev, shape):
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_attn_torch_arm_no_further_from_float64(dev, case):
     """SV_ATTN=torch (kernels.attn_*(torch_arm=True)): the same maths as torch ops on the same buffers."""
-    B, heads, N = shape
-    c = _case(shape)
-    e_hip = _errors(shape, *_run(dev, c["qkv"], c["dout"], B, N, heads))
-    e_t = _errors(shape, *_run(dev, c["qkv"], c["dout"], B, N, heads, torch_arm=True))
-    print(f"[attn] {shape}: torch arm " + ", ".join(f"{k} {v:.3e}" for k, v in e_t.items()))
+    (B, heads, N), _ = case
+    c = _case(case)
+    e_hip = _errors(case, *_run(dev, c["qkv"], c["dout"], B, N, heads))
+    e_t = _errors(case, *_run(dev, c["qkv"], c["dout"], B, N, heads, torch_arm=True))
+    print(f"[attn] {case}: torch arm " + ", ".join(f"{k} {v:.3e}" for k, v in e_t.items()))
     for name, v in e_t.items():
         if name.endswith("_abs"):
             assert v <= (1e-3 if name == "lse_abs" else 5e-6), (name, v)
@@ -190,7 +204,7 @@ def test_attn_padded_rows(dev, shape):
     zero, pad rows of the inputs (NaN here) never read."""
     B, heads, N = shape
     rows = (N + 7) // 8 * 8 + 8
-    c = _case(shape)
+    c = _case((shape, "uniform"))
     ref = _run(dev, c["qkv"], c["dout"], B, N, heads)
 
     def pad(t):

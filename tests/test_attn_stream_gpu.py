@@ -13,7 +13,12 @@ each of out, dq, dk, dv must be within max(1e-3, 3 x the restatement's error) in
 Inputs: q, k uniform in [-1.5, 1.5], v and dout uniform in [-1, 1], bf16-rounded.  Two more input sets at (2, 2, 257)
 scale the key rows by a ramp along the key index: rising (0.25 -> 1), so that the running max tends to keep growing
 up to the last key tile and every tile rescales the accumulator, and falling (1 -> 0.25), so that the max tends to sit
-in the first tile and later tiles rescale by one.
+in the first tile and later tiles rescale by one.  Two more at (2, 2, 257) shift every score of a head by +-98 and leave
+softmax unchanged in exact arithmetic: q[..., 0] = 28 for every query and k[..., 0] = +28 ("shift_up") or -28
+("shift_down") for every key, both exact in bf16, so the scaled scores lie in [94, 102] or [-102, -94] and lse is about
++-98 + log N: a forward without the max subtraction overflows or underflows, and a backward that mishandles a large lse
+loses P.  Same checks and the same bound rule; each own error of these two must stay below 2e-2 (measured on the CPU at
+N = 65 and 257: out 2.4e-3, dq 1.2e-2, dk 2.2e-3, dv 2.5e-3), so that the 3 x own bound cannot become vacuous.
 
 The measured figures of the first run are recorded in profiles/vit_hires/parity.txt."""
 import functools
@@ -27,7 +32,9 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 1), (2, 2, 33), (1, 1, 63), (1, 3, 64), (2, 2, 65), (1, 2, 127), (1, 1, 128), (1, 2, 129),
           (2, 3, 257), (1, 2, 577), (1, 1, 1025), (1, 1, 2048)]
-CASES = [(s, "uniform") for s in SHAPES] + [((2, 2, 257), "ramp_up"), ((2, 2, 257), "ramp_down")]
+CASES = [(s, "uniform") for s in SHAPES] + [((2, 2, 257), "ramp_up"), ((2, 2, 257), "ramp_down"),
+                                            ((2, 2, 257), "shift_up"), ((2, 2, 257), "shift_down")]
+SHIFT = 28.0  # exact in bf16; 28 * 28 * SCALE = 98
 IDS = ["x".join(map(str, s)) + ("" if v == "uniform" else "-" + v) for s, v in CASES]
 SCALE = 0.125
 SENTINEL = -7.0  # exactly representable in bf16 and f32
@@ -63,7 +70,11 @@ def _case(case):
     C = heads * 64
     qkv = torch.rand(B * N, 3 * C, generator=g, dtype=torch.float64) * 2 - 1
     qkv.view(B * N, 3, C)[:, :2] *= 1.5
-    if variant != "uniform":
+    if variant.startswith("shift"):
+        qk = qkv.view(B, N, 3, heads, 64)
+        qk[:, :, 0, :, 0] = SHIFT
+        qk[:, :, 1, :, 0] = SHIFT if variant == "shift_up" else -SHIFT
+    elif variant != "uniform":
         ramp = torch.linspace(0.25, 1.0, N, dtype=torch.float64)
         if variant == "ramp_down":
             ramp = ramp.flip(0)
@@ -148,6 +159,8 @@ def test_stream_against_float64(dev, case):
           + " | rounding-only restatement " + ", ".join(f"{k} {v:.3e}" for k, v in c["own"].items()))
     assert torch.isfinite(out.float()).all() and torch.isfinite(dqkv.float()).all() and torch.isfinite(lse).all(), \
         "an output element was not written (the outputs start as NaN) or is not finite"
+    if case[1].startswith("shift"):
+        assert all(v < 2e-2 for v in c["own"].values()), ("the restatement's own error makes the bound vacuous", c["own"])
     for name in ("out", "dq", "dk", "dv"):
         if name in e:
             assert e[name] <= _bound(case, name), (name, e[name], _bound(case, name))

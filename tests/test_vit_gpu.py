@@ -3,6 +3,13 @@ bounds: fp32 parity mode features < 1e-4 and every gradient against float64 with
 own error); bf16 teacher-forced per block outputs < 2e-2 and every input / parameter gradient < 0.15.  At 224 x 224
 (N = 197 tokens in Np = 200 rows) and, for speed, at 32 x 32 (N = 5 in 8 rows) and 80 x 80 (N = 26 in 32 rows).
 
+test_vit_bf16_block_against_restatement tightens the bf16 bound with the rule of tests/test_attn_gpu.py: the float64
+restatement of a block (_vit_ref.block_restated) rounds to bf16 exactly where the module stores bf16; its distance from
+float64 is what rounding alone causes, and the block output, dx and every parameter gradient of the first and last
+block must be within max(1e-3, 3 x that) of float64 in relative L2, for vit_tiny, deit_small, vit_base and vit_large at
+32 px with B = 2 and B = 8, and for vit_tiny and deit_small at 224 px with B = 8 (M = 1600 rows: the weight gradients
+leave the generic kernel for the bf16 split-K slabs).  Figures of the first run: profiles/vit_calls/parity.txt.
+
 The module keeps every image's tokens in rows padded to a multiple of 8 (DESIGN.md "ViT / DeiT-III"): the
 teacher-forced backward also checks that the pad rows of the block input gradient are exactly zero."""
 import copy
@@ -15,6 +22,7 @@ import _vit_ref as ref
 from oracle import weights as ow
 from spine_vision_amd import kernels as K
 from spine_vision_amd.backbone import create_vit
+from spine_vision_amd.backbone.vit import VIT_CFGS, ViTHip
 
 pytestmark = pytest.mark.gpu
 
@@ -135,6 +143,77 @@ def test_vit_bf16_teacher_forced(dev, name, size):
         x = o.detach()
     print(f"[vit parity] {name}@{size} B2 bf16: worst block output rel {worst_f:.2e}, worst block-backward rel "
           f"{worst_b:.2e}")
+
+
+RESTATED = [(n, 32, B) for n in ("vit_tiny", "deit_small", "vit_base", "vit_large") for B in (2, 8)] \
+    + [("vit_tiny", 224, 8), ("deit_small", 224, 8)]
+
+
+@functools.lru_cache(maxsize=2)
+def _filled(name, size):
+    """the filled fp32 reference module alone (no forward): shared by the B = 2 and B = 8 cases, never modified"""
+    return ow.fill_module(ref.create(name, size)).train()
+
+
+@pytest.mark.parametrize("name,size,B", RESTATED, ids=[f"{n}@{s}-B{B}" for n, s, B in RESTATED])
+def test_vit_bf16_block_against_restatement(dev, name, size, B):
+    """bf16 mode, the first and the last block, teacher-forced as test_vit_bf16_teacher_forced (the block input from
+    the fp32 reference chain, a fixed random output gradient) against the float64 block; bound: max(1e-3, 3 x the error
+    of the rounding-only restatement), for the block output, dx and every parameter gradient."""
+    r = _filled(name, size)
+    C, depth, heads, ls_init, no_embed_class = VIT_CFGS[name]
+    hip = ViTHip(C, 2, heads, ls_init=ls_init, no_embed_class=no_embed_class, img_size=size, precision="bf16")
+    hip.blocks[0].load_state_dict(r.blocks[0].state_dict(), strict=True)
+    hip.blocks[1].load_state_dict(r.blocks[depth - 1].state_dict(), strict=True)
+    hip = hip.to(dev).train()
+    N, Np = hip.num_tokens, hip.rows_per_img
+    M = B * Np
+    wg = hip._wgrads()
+
+    def slab_split(n, k):  # the host schedule of kernels.linear_wgrad / layerscale_wgrad for this module
+        split = K._wgrad_split_for(n, k, M, hip.wgrad_target)
+        return split if K._bf16_slabs(n, k, M, split, True, wg.spol) else 1
+
+    with torch.no_grad():
+        x = r.tokens(_image(B, size))
+        inputs = {}
+        for i, rb in enumerate(r.blocks):
+            if i in (0, depth - 1):
+                inputs[i] = x
+            x = rb(x)
+    worst = 0.0
+    for j, i in enumerate((0, depth - 1)):
+        rb, hb, x = r.blocks[i], hip.blocks[j], inputs[i]
+        b64 = copy.deepcopy(rb).double()
+        xr = x.double().requires_grad_(True)
+        o = b64(xr)
+        d = torch.randn(o.shape, generator=torch.Generator().manual_seed(i))
+        o.backward(d.double())
+        f64 = {"out": o.detach(), "dx": xr.grad, **{n: p.grad for n, p in b64.named_parameters()}}
+        rs = ref.block_restated(rb, x, d, rows_per_img=Np, slab_split=slab_split)
+        own = {"out": rel(rs["out"], f64["out"]), "dx": rel(rs["dx"], f64["dx"]),
+               **{n: rel(g, f64[n]) for n, g in rs["grads"].items()}}
+        for p in hb.parameters():
+            p.grad = torch.zeros_like(p)
+        with torch.no_grad():
+            xo, saved = hip._block_forward(hb, _pad_rows(x, Np).to(dev), B, {}, save=True)
+            dx = hip._block_backward(hb, saved, _pad_rows(d, Np).to(dev), B, wg, {}, ready=False)
+            wg.join()
+        torch.cuda.synchronize()
+        dx = dx.view(B, Np, -1)
+        assert bool((dx[:, N:] == 0).all()), f"block {i}: pad rows of the input gradient are not zero"
+        got = {"out": xo.view(B, Np, -1)[:, :N], "dx": dx[:, :N], **{n: p.grad for n, p in hb.named_parameters()}}
+        assert sorted(got) == sorted(f64) == sorted(own)
+        errs = {n: rel(got[n], f64[n]) for n in f64}
+        slabs = sorted(n for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")
+                       if slab_split(*dict(hb.named_parameters())[n + ".weight"].shape) > 1)
+        print(f"[vit restated] {name}@{size} B{B} block {i} (M = {M}, bf16 slabs: {', '.join(slabs) or 'none'}): "
+              "kernel / restatement error: " + ", ".join(f"{n} {errs[n]:.2e} / {own[n]:.2e}" for n in f64))
+        for n in f64:
+            bound = max(1e-3, 3.0 * own[n])
+            worst = max(worst, errs[n] / bound)
+            assert errs[n] <= bound, (name, size, B, i, n, errs[n], own[n])
+    print(f"[vit restated] {name}@{size} B{B}: worst error / bound {worst:.3f}")
 
 
 def test_patchify16_bitwise(dev):
