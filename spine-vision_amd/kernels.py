@@ -1344,12 +1344,13 @@ def _slab_finish(work: torch.Tensor, split: int, M: int, N: int, C: torch.Tensor
                 N, ptr(C), dt(C), N, int(accumulate), ptr(stats))
 
 
-def _pointwise_fwd(x, wp, s, y, M, stats=None, policy=None):
+def _pointwise_fwd(x, wp, s, y, M, stats=None, policy=None, work=None):
     """1x1 conv forward as a GEMM over [M, Cs] rows; split-K + slab finish when the grid is small."""
     split = _conv_split(M, s.Cout, s.Cs)
     x2d, w2d = x.view(M, s.Cs), wp.view(s.Cout, s.Cs)
     if split > 1:
-        work = torch.empty(split * M * s.Cout, device=x.device, dtype=torch.float32)
+        work = (torch.empty(split * M * s.Cout, device=x.device, dtype=torch.float32) if work is None
+                else _conv_work(work, split * M * s.Cout, x.device, "conv_fwd")[:split * M * s.Cout])
         linear_fwd(x2d, w2d, out=work, epilogue=nv.SV_EPI_SLAB, split_k=split, policy=policy)
         _slab_finish(work, split, M, s.Cout, y, stats=stats)
     elif stats is not None:
@@ -1358,19 +1359,42 @@ def _pointwise_fwd(x, wp, s, y, M, stats=None, policy=None):
         linear_fwd(x2d, w2d, out=y.view(M, s.Cout), policy=policy)
 
 
+def _conv_buf(t, shape: tuple, dtype: torch.dtype, device, who: str) -> torch.Tensor:
+    """the caller's ``out=`` / ``part=`` buffer, checked (callers allocate a fresh one when none is given)"""
+    _check(t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.device == device,
+           f"{who} must be contiguous {dtype} {tuple(shape)}, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _conv_work(work, n: int, device, who: str) -> torch.Tensor:
+    """the caller's f32 ``work=`` space of at least n floats, checked (callers allocate a fresh one when none is given)"""
+    _check(work.is_contiguous() and work.dtype == torch.float32 and work.numel() >= n and work.device == device,
+           f"{who}: work must be contiguous f32 with at least {n} elements")
+    return work
+
+
 def conv_fwd(x: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, out_dtype: torch.dtype,
-             policy: "nv.GemmPolicy | None" = None) -> torch.Tensor:
+             policy: "nv.GemmPolicy | None" = None, *, out: torch.Tensor | None = None,
+             work: torch.Tensor | None = None, split: int | None = None) -> torch.Tensor:
+    """``out`` / ``work``: the output and the split-K slab space (default: fresh allocations); ``split``: the slice
+    count of the gathered split-K form (default: the host schedule ``_conv_split``)."""
     _conv_check_x(x, s, wp.dtype, "conv_fwd")
     _check(tuple(wp.shape) == (s.Cout, s.KH * s.KW, s.Cs), "conv_fwd: packed weight shape")
     OH, OW = conv_out_hw(s.H, s.W, s.KH, s.stride, s.pad)
-    y = torch.empty(s.B, OH, OW, s.Cout, device=x.device, dtype=out_dtype)
+    y = (torch.empty(s.B, OH, OW, s.Cout, device=x.device, dtype=out_dtype) if out is None
+         else _conv_buf(out, (s.B, OH, OW, s.Cout), out_dtype, x.device, "conv_fwd: out"))
     if _pointwise(s, wp.dtype):
-        _pointwise_fwd(x, wp, s, y, s.B * s.H * s.W, policy=policy)
+        _check(split is None, "conv_fwd: split applies to the gathered path")
+        _pointwise_fwd(x, wp, s, y, s.B * s.H * s.W, policy=policy, work=work)
         return y
     M, K = s.B * OH * OW, s.KH * s.KW * s.Cs
-    split = _conv_split(M, s.Cout, K, _CONV_FWD_MIN_KSTEPS) if _gathered(s, wp.dtype) else 1
+    if split is None:
+        split = _conv_split(M, s.Cout, K, _CONV_FWD_MIN_KSTEPS) if _gathered(s, wp.dtype) else 1
+    else:
+        _check(_gathered(s, wp.dtype) and 1 <= split <= K // 32, "conv_fwd: split needs the gathered path")
     if split > 1:
-        work = torch.empty(split * M * s.Cout, device=x.device, dtype=torch.float32)
+        work = (torch.empty(split * M * s.Cout, device=x.device, dtype=torch.float32) if work is None
+                else _conv_work(work, split * M * s.Cout, x.device, "conv_fwd"))
         call("sv_conv_fwd_split", ptr(x), ptr(wp), ptr(y), dt(y), dt(wp), ctypes.byref(s), None, ptr(work), split,
              nv.pol_ref(policy))
         return y
@@ -1391,31 +1415,43 @@ def _ones(n: int, device: torch.device) -> torch.Tensor:
 
 
 def conv_fwd_bn_stats(x: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, out_dtype: torch.dtype,
-                      policy: "nv.GemmPolicy | None" = None):
+                      policy: "nv.GemmPolicy | None" = None, *, out: torch.Tensor | None = None,
+                      part: torch.Tensor | None = None, work: torch.Tensor | None = None, split: int | None = None):
     """conv_fwd plus the train-mode BatchNorm statistics of y straight from the GEMM epilogue
     (SV_EPI_STORE_STATS: no separate read pass over y) -> (y, partials [ceil(M/64)][2][Cout] f32), or
-    (y, None) when the conv runs on a path without that epilogue (then use bn_stats(y))."""
+    (y, None) when the conv runs on a path without that epilogue (then use bn_stats(y)).
+    ``out`` / ``part`` / ``work`` / ``split``: as conv_fwd's (``part``: the partials buffer)."""
     if wp.dtype != torch.bfloat16 or out_dtype != torch.bfloat16 or s.Cout % 8:
-        return conv_fwd(x, wp, s, out_dtype, policy), None
+        return conv_fwd(x, wp, s, out_dtype, policy, out=out, work=work, split=split), None
     OH, OW = conv_out_hw(s.H, s.W, s.KH, s.stride, s.pad)
     M = s.B * OH * OW
     if _pointwise(s, wp.dtype):
         if s.Cs % 32:
-            return conv_fwd(x, wp, s, out_dtype, policy), None
+            return conv_fwd(x, wp, s, out_dtype, policy, out=out, work=work, split=split), None
+        _check(split is None, "conv_fwd: split applies to the gathered path")
         _conv_check_x(x, s, wp.dtype, "conv_fwd")
-        y = torch.empty(s.B, OH, OW, s.Cout, device=x.device, dtype=out_dtype)
-        part = torch.empty((M + 63) // 64, 2, s.Cout, device=x.device, dtype=torch.float32)
-        _pointwise_fwd(x, wp, s, y, M, stats=part, policy=policy)
+        y = (torch.empty(s.B, OH, OW, s.Cout, device=x.device, dtype=out_dtype) if out is None
+             else _conv_buf(out, (s.B, OH, OW, s.Cout), out_dtype, x.device, "conv_fwd: out"))
+        part = (torch.empty((M + 63) // 64, 2, s.Cout, device=x.device, dtype=torch.float32) if part is None
+                else _conv_buf(part, ((M + 63) // 64, 2, s.Cout), torch.float32, x.device, "conv_fwd_bn_stats: part"))
+        _pointwise_fwd(x, wp, s, y, M, stats=part, policy=policy, work=work)
         return y, part
     if not (_gathered(s, wp.dtype) or _stem8(s, wp.dtype)):
-        return conv_fwd(x, wp, s, out_dtype, policy), None
+        return conv_fwd(x, wp, s, out_dtype, policy, out=out, work=work, split=split), None
     _conv_check_x(x, s, wp.dtype, "conv_fwd")
     _check(tuple(wp.shape) == (s.Cout, s.KH * s.KW, s.Cs), "conv_fwd: packed weight shape")
-    y = torch.empty(s.B, OH, OW, s.Cout, device=x.device, dtype=out_dtype)
-    part = torch.empty((M + 63) // 64, 2, s.Cout, device=x.device, dtype=torch.float32)
-    split = 1 if _stem8(s, wp.dtype) else _conv_split(M, s.Cout, s.KH * s.KW * s.Cs, _CONV_FWD_MIN_KSTEPS)
+    y = (torch.empty(s.B, OH, OW, s.Cout, device=x.device, dtype=out_dtype) if out is None
+         else _conv_buf(out, (s.B, OH, OW, s.Cout), out_dtype, x.device, "conv_fwd: out"))
+    part = (torch.empty((M + 63) // 64, 2, s.Cout, device=x.device, dtype=torch.float32) if part is None
+            else _conv_buf(part, ((M + 63) // 64, 2, s.Cout), torch.float32, x.device, "conv_fwd_bn_stats: part"))
+    if split is None:
+        split = 1 if _stem8(s, wp.dtype) else _conv_split(M, s.Cout, s.KH * s.KW * s.Cs, _CONV_FWD_MIN_KSTEPS)
+    else:
+        _check(_gathered(s, wp.dtype) and 1 <= split <= s.KH * s.KW * s.Cs // 32,
+               "conv_fwd: split needs the gathered path")
     if split > 1:
-        work = torch.empty(split * M * s.Cout, device=x.device, dtype=torch.float32)
+        work = (torch.empty(split * M * s.Cout, device=x.device, dtype=torch.float32) if work is None
+                else _conv_work(work, split * M * s.Cout, x.device, "conv_fwd"))
         call("sv_conv_fwd_split", ptr(x), ptr(wp), ptr(y), dt(y), dt(wp), ctypes.byref(s), ptr(part), ptr(work), split,
              nv.pol_ref(policy))
     else:
@@ -1437,7 +1473,8 @@ def bn_stats_from_partials(part: torch.Tensor, rows: int, *, eps: float = EPS_BN
 
 def conv_bwd_data(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, *, dx: torch.Tensor | None = None,
                   accumulate: bool = False, dx_dtype: torch.dtype = torch.float32,
-                  policy: "nv.GemmPolicy | None" = None) -> torch.Tensor:
+                  policy: "nv.GemmPolicy | None" = None, work: torch.Tensor | None = None) -> torch.Tensor:
+    """``work``: the slab space of the split-K and the stride-2 scatter forms (default: a fresh allocation)"""
     OH, OW = conv_out_hw(s.H, s.W, s.KH, s.stride, s.pad)
     _check(dy.is_contiguous() and tuple(dy.shape) == (s.B, OH, OW, s.Cout) and dy.dtype == wp.dtype,
            "conv_bwd_data: dy must be contiguous [B,OH,OW,Cout] in the compute dtype")
@@ -1451,7 +1488,8 @@ def conv_bwd_data(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, *, dx: to
         split = _conv_split(M, s.Cs, s.Cout)
         dy2d, w2d = dy.view(M, s.Cout), wp.view(s.Cout, s.Cs)
         if split > 1:
-            work = torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32)
+            work = (torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32) if work is None
+                    else _conv_work(work, split * M * s.Cs, dy.device, "conv_bwd_data")[:split * M * s.Cs])
             linear_dgrad(dy2d, w2d, out=work, epilogue=nv.SV_EPI_SLAB, split_k=split, policy=policy)
             _slab_finish(work, split, M, s.Cs, dx, accumulate=accumulate)
         elif accumulate:  # dx += dy W: the layer-scale/residual epilogue with gamma = 1, residual = dx (in place)
@@ -1467,7 +1505,8 @@ def conv_bwd_data(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, *, dx: to
         M = s.B * s.H * s.W
         split = _conv_split(M, s.Cs, T * s.Cout)
         if split > 1:
-            work = torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32)
+            work = (torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32) if work is None
+                    else _conv_work(work, split * M * s.Cs, dy.device, "conv_bwd_data"))
             call("sv_conv_bwd_data_split", ptr(dy), ptr(wp), ptr(dx), dt(dx), int(accumulate), dt(wp),
                  ctypes.byref(s), ptr(work), split, nv.pol_ref(policy))
             return dx
@@ -1481,7 +1520,8 @@ def conv_bwd_data(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, *, dx: to
             call("sv_conv_bwd_data", ptr(dy), ptr(wp), ptr(dx), dt(dx), int(accumulate), dt(wp), ctypes.byref(s),
                  nv.pol_ref(policy))
             return dx
-        work = torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32)
+        work = (torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32) if work is None
+                else _conv_work(work, split * M * s.Cs, dy.device, "conv_bwd_data"))
         call("sv_conv_bwd_data_split", ptr(dy), ptr(wp), ptr(dx), dt(dx), int(accumulate), dt(wp),
              ctypes.byref(s), ptr(work), split, nv.pol_ref(policy))
         return dx
@@ -1515,7 +1555,8 @@ def _al16(*ts) -> bool:
 
 def conv_bwd_data_bn(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, y: torch.Tensor, mean: torch.Tensor,
                      rstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, unsplit: bool = True,
-                     policy: "nv.GemmPolicy | None" = None):
+                     policy: "nv.GemmPolicy | None" = None, out: torch.Tensor | None = None,
+                     part: torch.Tensor | None = None, work: torch.Tensor | None = None):
     """conv_bwd_data (bf16 dx, no accumulate) fused with the backward statistics of the BatchNorm + ReLU that
     produced the conv's input: y [B,H,W,Cs] is that BatchNorm's input (bf16), mean / rstd its batch statistics,
     gamma / beta its affine parameters.  -> (dx, part), part = f32 [ceil(B*H*W/64)][2][Cs] partial sums of g
@@ -1524,7 +1565,8 @@ def conv_bwd_data_bn(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, y: tor
     statistics pass over dx and y.  ``unsplit=False`` fuses the split-K shapes only.  Stride 2 (even H, W,
     no split): the one-launch parity-class GEMM with the same epilogue, 4 * ceil(B*H*W/256) partial rows
     (one run per class).  None when the shape is not on these paths (odd stride-2 grids, split stride-2
-    shapes, fp32, unaligned parameters): use conv_bwd_data + bn_bwd."""
+    shapes, fp32, unaligned parameters): use conv_bwd_data + bn_bwd.  ``out`` / ``part`` / ``work``: dx, the partials
+    and the split-K slab space (default: fresh allocations)."""
     if wp.dtype != torch.bfloat16 or y.dtype != torch.bfloat16 or s.Cs % 8 or s.stride not in (1, 2):
         return None
     M = s.B * s.H * s.W
@@ -1552,10 +1594,17 @@ def conv_bwd_data_bn(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, y: tor
     if not _al16(y, *prm) or any(p_.dtype != torch.float32 or not p_.is_contiguous() for p_ in prm):
         return None
     ref = nv.BnRef(ptr(prm[0]), ptr(prm[1]), ptr(prm[2]), ptr(prm[3]))
-    dx = torch.empty(s.B, s.H, s.W, s.Cs, device=dy.device, dtype=torch.bfloat16)
+    dx = (torch.empty(s.B, s.H, s.W, s.Cs, device=dy.device, dtype=torch.bfloat16) if out is None
+          else _conv_buf(out, (s.B, s.H, s.W, s.Cs), torch.bfloat16, dy.device, "conv_bwd_data_bn: out"))
     prows = 4 * ((M // 4 + 63) // 64) if s2 else (M + 63) // 64
-    part = torch.empty(prows, 2, s.Cs, device=dy.device, dtype=torch.float32)
-    work = torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32) if split > 1 else None
+    part = (torch.empty(prows, 2, s.Cs, device=dy.device, dtype=torch.float32) if part is None
+            else _conv_buf(part, (prows, 2, s.Cs), torch.float32, dy.device, "conv_bwd_data_bn: part"))
+    if split == 1:
+        work = None
+    elif work is None:
+        work = torch.empty(split * M * s.Cs, device=dy.device, dtype=torch.float32)
+    else:
+        work = _conv_work(work, split * M * s.Cs, dy.device, "conv_bwd_data_bn")[:split * M * s.Cs]
     if pw and split > 1:
         linear_dgrad(dy.view(M, s.Cout), wp.view(s.Cout, s.Cs), out=work, epilogue=nv.SV_EPI_SLAB, split_k=split,
                      policy=policy)
@@ -1570,7 +1619,9 @@ def conv_bwd_data_bn(dy: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, y: tor
 
 
 def conv_bwd_weight(dy: torch.Tensor, x: torch.Tensor, s: nv.ConvShape, *, dw: torch.Tensor,
-                    accumulate: bool = True, policy: "nv.GemmPolicy | None" = None) -> torch.Tensor:
+                    accumulate: bool = True, policy: "nv.GemmPolicy | None" = None,
+                    work: torch.Tensor | None = None) -> torch.Tensor:
+    """``work``: the split-K slab space, sv_conv_bwd_weight_work_floats(s) floats (default: a fresh allocation)"""
     OH, OW = conv_out_hw(s.H, s.W, s.KH, s.stride, s.pad)
     _conv_check_x(x, s, dy.dtype, "conv_bwd_weight")
     _check(dy.is_contiguous() and tuple(dy.shape) == (s.B, OH, OW, s.Cout), "conv_bwd_weight: dy shape")
@@ -1582,7 +1633,8 @@ def conv_bwd_weight(dy: torch.Tensor, x: torch.Tensor, s: nv.ConvShape, *, dw: t
                      compute_bf16=True, policy=policy)
         return dw
     nwork = value("sv_conv_bwd_weight_work_floats", ctypes.byref(s))
-    work = torch.empty(nwork, device=dy.device, dtype=torch.float32)
+    work = (torch.empty(nwork, device=dy.device, dtype=torch.float32) if work is None
+            else _conv_work(work, nwork, dy.device, "conv_bwd_weight"))
     call("sv_conv_bwd_weight", ptr(dy), ptr(x), ptr(work), ptr(dw), int(accumulate), dt(dy), ctypes.byref(s),
          nv.pol_ref(policy))
     return dw
