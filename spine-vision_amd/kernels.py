@@ -1460,12 +1460,16 @@ def conv_fwd_bn_stats(x: torch.Tensor, wp: torch.Tensor, s: nv.ConvShape, out_dt
 
 
 def bn_stats_from_partials(part: torch.Tensor, rows: int, *, eps: float = EPS_BN, momentum: float = 0.1,
-                           running_mean=None, running_var=None, num_batches_tracked=None):
-    """(mean, rstd) from conv_fwd_bn_stats' unshifted partials; running stats updated like bn_stats."""
+                           running_mean=None, running_var=None, num_batches_tracked=None, out: tuple | None = None):
+    """(mean, rstd) from conv_fwd_bn_stats' unshifted partials; running stats updated like bn_stats.
+    ``out``: the caller's (mean, rstd) f32 [C] buffers (default: fresh allocations)."""
     P, two, C = part.shape
     _check(two == 2 and part.dtype == torch.float32 and part.is_contiguous(), "bn_stats_from_partials: bad partials")
-    mean = torch.empty(C, device=part.device, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
+    if out is None:
+        mean = torch.empty(C, device=part.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+    else:
+        mean, rstd = _bn_stat_out(out, C, part.device, "bn_stats_from_partials")
     _fin("sv_bn_stats_finish", None, SV_F32, ptr(part), P, rows, C, float(eps), float(momentum), ptr(mean),
          ptr(rstd), ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), *_fin_ws(part.device))
     return mean, rstd
@@ -1776,26 +1780,41 @@ def _bn_c_ok(C: int) -> bool:
     return C >= 4 and C % 4 == 0 and (C // 4 <= 256 or (C // 4) % 256 == 0)
 
 
+# The caller's ``out=`` / ``part=`` / ``sums=`` buffers of the BatchNorm and pooling wrappers are checked with _conv_buf;
+# without one, each wrapper evaluates the same torch.empty expression as before
+def _bn_stat_out(out, C: int, device, who: str) -> tuple:
+    return tuple(_conv_buf(t, (C,), torch.float32, device, f"{who}: out") for t in out)
+
+
 def bn_stats(y2d: torch.Tensor, *, eps: float = EPS_BN, momentum: float = 0.1, running_mean=None, running_var=None,
-             num_batches_tracked=None):
+             num_batches_tracked=None, out: tuple | None = None, part: torch.Tensor | None = None):
     """Train-mode batch statistics of y [rows, C] -> (mean, rstd) f32; running stats (and the int64
-    num_batches_tracked counter) updated in place on the device."""
+    num_batches_tracked counter) updated in place on the device.  ``out`` / ``part``: the caller's (mean, rstd) and
+    partials [sv_bn_nparts][2][C] buffers (default: fresh allocations)."""
     rows, C = y2d.shape
     _check(_bn_c_ok(C) and y2d.is_contiguous() and rows > 0, f"bn_stats: unsupported C={C}")
     P = value("sv_bn_nparts", rows, C)
-    part = torch.empty(P, 2, C, device=y2d.device, dtype=torch.float32)
+    part = (torch.empty(P, 2, C, device=y2d.device, dtype=torch.float32) if part is None
+            else _conv_buf(part, (P, 2, C), torch.float32, y2d.device, "bn_stats: part"))
     call("sv_bn_stats", ptr(y2d), dt(y2d), rows, C, ptr(part))
-    mean = torch.empty(C, device=y2d.device, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
+    if out is None:
+        mean = torch.empty(C, device=y2d.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+    else:
+        mean, rstd = _bn_stat_out(out, C, y2d.device, "bn_stats")
     _fin("sv_bn_stats_finish", ptr(y2d), dt(y2d), ptr(part), P, rows, C, float(eps), float(momentum), ptr(mean),
          ptr(rstd), ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), *_fin_ws(part.device))
     return mean, rstd
 
 
-def bn_eval_params(running_mean: torch.Tensor, running_var: torch.Tensor, eps: float = EPS_BN):
+def bn_eval_params(running_mean: torch.Tensor, running_var: torch.Tensor, eps: float = EPS_BN,
+                   out: tuple | None = None):
     C = running_mean.numel()
-    mean = torch.empty(C, device=running_mean.device, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
+    if out is None:
+        mean = torch.empty(C, device=running_mean.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+    else:
+        mean, rstd = _bn_stat_out(out, C, running_mean.device, "bn_eval_params")
     call("sv_bn_eval_params", ptr(running_mean), ptr(running_var), float(eps), ptr(mean), ptr(rstd), C)
     return mean, rstd
 
@@ -1955,11 +1974,15 @@ def bn_act_small(y2d, part, bn_params: tuple, *, res=None, res_part=None, res_pa
 # The two wide BatchNorm backward entry points, marshalled once each: operands a call site does not name are NULL / 0.
 # ``y2 / mean2 / rstd2 / gamma2`` (the DUAL mode's second BatchNorm) make the result (dx, dx2).
 def _bn_bwd_small(mode, dout, y, mean, rstd, gamma, *, dx_dtype, batch_stats, act=None, beta=None, y2=None, mean2=None,
-                  rstd2=None, gamma2=None, part=None, dgamma=None, dbeta=None, dgamma2=None, dbeta2=None):
+                  rstd2=None, gamma2=None, part=None, dgamma=None, dbeta=None, dgamma2=None, dbeta2=None, out=None,
+                  out2=None):
     """The whole BatchNorm backward in one launch (sv_bn_bwd_small); ``part``: statistics partials already summed."""
     rows, C = y.shape
-    dx = torch.empty(rows, C, device=y.device, dtype=dx_dtype)
-    dx2 = torch.empty_like(dx) if y2 is not None else None
+    dx = (torch.empty(rows, C, device=y.device, dtype=dx_dtype) if out is None
+          else _conv_buf(out, (rows, C), dx_dtype, y.device, "bn_bwd: out"))
+    dx2 = None
+    if y2 is not None:
+        dx2 = (torch.empty_like(dx) if out2 is None else _conv_buf(out2, (rows, C), dx_dtype, y.device, "bn_bwd: out"))
     call("sv_bn_bwd_small", mode, ptr(dout), dt(dout), ptr(act), nv.dt_none(act), ptr(y), dt(y), ptr(mean), ptr(rstd),
          ptr(gamma), ptr(beta), ptr(y2), dt(y2) if y2 is not None else 0, ptr(mean2), ptr(rstd2), ptr(gamma2),
          ptr(part), part.shape[0] if part is not None else 0, ptr(dx), ptr(dx2), dt(dx), ptr(dgamma), ptr(dbeta),
@@ -1969,12 +1992,15 @@ def _bn_bwd_small(mode, dout, y, mean, rstd, gamma, *, dx_dtype, batch_stats, ac
 
 def _bn_bwd_apply_fold(mode, dout, y, mean, rstd, gamma, part, P, *, dx_dtype, batch_stats, idx=None, H=0, W=0,
                        beta=None, y2=None, mean2=None, rstd2=None, gamma2=None, part2=None, dgamma=None, dbeta=None,
-                       dgamma2=None, dbeta2=None):
+                       dgamma2=None, dbeta2=None, out=None, out2=None):
     """The statistics finish inside the apply pass (sv_bn_bwd_apply_fold); ``idx / H / W``: dout is a max-pool's
     output gradient, gathered through the pool's indices."""
     rows, C = y.shape
-    dx = torch.empty(rows, C, device=y.device, dtype=dx_dtype)
-    dx2 = torch.empty_like(dx) if y2 is not None else None
+    dx = (torch.empty(rows, C, device=y.device, dtype=dx_dtype) if out is None
+          else _conv_buf(out, (rows, C), dx_dtype, y.device, "bn_bwd: out"))
+    dx2 = None
+    if y2 is not None:
+        dx2 = (torch.empty_like(dx) if out2 is None else _conv_buf(out2, (rows, C), dx_dtype, y.device, "bn_bwd: out"))
     _fin("sv_bn_bwd_apply_fold", mode, ptr(dout), dt(dout), ptr(idx), H, W, ptr(y), dt(y), ptr(mean), ptr(rstd),
          ptr(gamma), ptr(beta), ptr(y2), dt(y2) if y2 is not None else 0, ptr(mean2), ptr(rstd2), ptr(gamma2),
          ptr(part), ptr(part2), P, ptr(dx), ptr(dx2), dt(dx), ptr(dgamma), ptr(dbeta), ptr(dgamma2), ptr(dbeta2),
@@ -1982,11 +2008,12 @@ def _bn_bwd_apply_fold(mode, dout, y, mean, rstd, gamma, part, P, *, dx_dtype, b
     return dx if y2 is None else (dx, dx2)
 
 
-def _bn_bwd_sums(P: int, C: int, batch_stats: bool, *folds) -> torch.Tensor:
+def _bn_bwd_sums(P: int, C: int, batch_stats: bool, *folds, sums: torch.Tensor | None = None) -> torch.Tensor:
     """The separate finish: one sv_bn_bwd_finish per (part, dgamma, dbeta) of ``folds`` into ONE buffer -> sums
     [len(folds)][2][C] for the apply pass (dgamma / dbeta accumulate); eval mode zeroes it with one launch."""
     dev = folds[0][0].device
-    sums = torch.empty(len(folds), 2, C, device=dev, dtype=torch.float32)
+    sums = (torch.empty(len(folds), 2, C, device=dev, dtype=torch.float32) if sums is None
+            else _conv_buf(sums, (len(folds), 2, C), torch.float32, dev, "bn_bwd: sums"))
     ws = _fin_ws(dev)
     for i, (part, dgamma, dbeta) in enumerate(folds):  # into sums[i] (2 * C floats each), without a view per fold
         _fin("sv_bn_bwd_finish", ptr(part), P, C, ptr(sums) + i * 8 * C, ptr(dgamma), ptr(dbeta), *ws)
@@ -1997,7 +2024,8 @@ def _bn_bwd_sums(P: int, C: int, batch_stats: bool, *folds) -> torch.Tensor:
 
 def bn_bwd(dout2d, y2d, mean, rstd, gamma, *, act=None, relu_beta=None, dgamma=None, dbeta=None,
            dx_dtype=torch.float32, gmask=None, mask_inplace: bool = False, batch_stats: bool = True,
-           part: torch.Tensor | None = None) -> torch.Tensor:
+           part: torch.Tensor | None = None, out: torch.Tensor | None = None, work: torch.Tensor | None = None,
+           sums: torch.Tensor | None = None) -> torch.Tensor:
     """BatchNorm backward with an optional ReLU mask on dout; dgamma/dbeta accumulate.  The mask is
     act > 0, or -- ``relu_beta`` = the BN's beta, for a BN followed by its own ReLU -- recomputed from y
     like the forward's pre-activation (sv_bn_relu_bwd_*: the activation is not read again).
@@ -2008,7 +2036,9 @@ def bn_bwd(dout2d, y2d, mean, rstd, gamma, *, act=None, relu_beta=None, dgamma=N
     False: eval mode (running statistics, an affine map: dx = gamma * rstd * dout, the apply kernel reading
     zero correction sums).
     ``part`` (relu_beta form): the backward statistics' partials [P][2][C] already summed by the producer of
-    dout (conv_bwd_data_bn), so the statistics pass is skipped."""
+    dout (conv_bwd_data_bn), so the statistics pass is skipped.
+    ``out`` / ``work`` / ``sums``: the caller's dx, statistics partials [sv_bn_nparts][2][C] (where ``part`` is not
+    given) and folded sums [1][2][C] buffers (default: fresh allocations)."""
     rows, C = y2d.shape
     _check(_bn_c_ok(C) and dout2d.numel() == rows * C and dout2d.is_contiguous(), "bn_bwd: bad shapes")
     _check(act is None or relu_beta is None, "bn_bwd: act and relu_beta are exclusive")
@@ -2027,12 +2057,13 @@ def bn_bwd(dout2d, y2d, mean, rstd, gamma, *, act=None, relu_beta=None, dgamma=N
     if (small_mode is not None and gmask is None and bn_small_ok(rows, C)
             and _bn_small_args_ok(dout2d, y2d, mean, rstd, gamma, act, relu_beta, part, dgamma, dbeta)):
         return _bn_bwd_small(small_mode, dout2d, y2d, mean, rstd, gamma, act=act, beta=relu_beta, part=part,
-                             dgamma=dgamma, dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats)
+                             dgamma=dgamma, dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats, out=out)
     if part is not None:  # summed by dout's producer (conv_bwd_data_bn)
         P = part.shape[0]
     else:
         P = value("sv_bn_nparts", rows, C)
-        part = torch.empty(P, 2, C, device=y2d.device, dtype=torch.float32)
+        part = (torch.empty(P, 2, C, device=y2d.device, dtype=torch.float32) if work is None
+                else _conv_buf(work, (P, 2, C), torch.float32, y2d.device, "bn_bwd: work"))
         if relu_beta is not None:
             call("sv_bn_relu_bwd_stats", ptr(dout2d), dt(dout2d), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma),
                  ptr(relu_beta), rows, C, ptr(part))
@@ -2048,9 +2079,10 @@ def bn_bwd(dout2d, y2d, mean, rstd, gamma, *, act=None, relu_beta=None, dgamma=N
         # MASK = dout already masked (mask_inplace)
         mode = nv.SV_BN_SMALL_RELU if relu_beta is not None else nv.SV_BN_SMALL_MASK
         return _bn_bwd_apply_fold(mode, dout2d, y2d, mean, rstd, gamma, part, P, beta=relu_beta, dgamma=dgamma,
-                                  dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats)
-    sums = _bn_bwd_sums(P, C, batch_stats, (part, dgamma, dbeta))
-    dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
+                                  dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats, out=out)
+    sums = _bn_bwd_sums(P, C, batch_stats, (part, dgamma, dbeta), sums=sums)
+    dx = (torch.empty(rows, C, device=y2d.device, dtype=dx_dtype) if out is None
+          else _conv_buf(out, (rows, C), dx_dtype, y2d.device, "bn_bwd: out"))
     if relu_beta is not None:
         call("sv_bn_relu_bwd_apply", ptr(dout2d), dt(dout2d), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma),
              ptr(relu_beta), ptr(sums), ptr(dx), dt(dx), rows, C)
@@ -2061,53 +2093,67 @@ def bn_bwd(dout2d, y2d, mean, rstd, gamma, *, act=None, relu_beta=None, dgamma=N
 
 
 def bn_bwd_dual(gm, y2d, mean, rstd, gamma, act, y2, mean2, rstd2, gamma2, *, dgamma=None, dbeta=None,
-                dgamma2=None, dbeta2=None, dx_dtype=torch.float32, batch_stats: bool = True):
+                dgamma2=None, dbeta2=None, dx_dtype=torch.float32, batch_stats: bool = True,
+                out: tuple | None = None, part: torch.Tensor | None = None, sums: torch.Tensor | None = None):
     """A projection-shortcut block's two output BatchNorms from one masked gradient: equals
     ``bn_bwd(gm, y2d, ..., act=act, mask_inplace=True)`` followed by ``bn_bwd(gm, y2, mean2, rstd2, gamma2)``
     bit for bit (gm, f32 or bf16, is overwritten with the masked gradient the same way), with gm read once per pass
-    instead of twice (sv_bn_bwd_stats_mask_dual / sv_bn_bwd_apply_dual). -> (dx, dx2)."""
+    instead of twice (sv_bn_bwd_stats_mask_dual / sv_bn_bwd_apply_dual). -> (dx, dx2).
+    ``out`` / ``part`` / ``sums``: the caller's (dx, dx2), partials [2][sv_bn_nparts][2][C] and folded sums [2][2][C]
+    buffers (default: fresh allocations)."""
     rows, C = y2d.shape
     _check(_bn_c_ok(C) and gm.dtype in (torch.float32, torch.bfloat16) and gm.numel() == rows * C and gm.is_contiguous()
            and act.numel() == rows * C and act.is_contiguous() and y2.numel() == rows * C and y2.is_contiguous(),
            "bn_bwd_dual: bad shapes")
     both = dict(y2=y2, mean2=mean2, rstd2=rstd2, gamma2=gamma2, dgamma=dgamma, dbeta=dbeta, dgamma2=dgamma2,
                 dbeta2=dbeta2, dx_dtype=dx_dtype, batch_stats=batch_stats)
+    o1, o2 = out if out is not None else (None, None)
     if bn_small_ok(rows, C) and _bn_small_args_ok(gm, y2d, mean, rstd, gamma, act, y2, mean2, rstd2, gamma2, dgamma,
                                                    dbeta, dgamma2, dbeta2):
-        return _bn_bwd_small(nv.SV_BN_SMALL_DUAL, gm, y2d, mean, rstd, gamma, act=act, **both)
+        return _bn_bwd_small(nv.SV_BN_SMALL_DUAL, gm, y2d, mean, rstd, gamma, act=act, out=o1, out2=o2, **both)
     P = value("sv_bn_nparts", rows, C)
-    part = torch.empty(2, P, 2, C, device=y2d.device, dtype=torch.float32)
+    part = (torch.empty(2, P, 2, C, device=y2d.device, dtype=torch.float32) if part is None
+            else _conv_buf(part, (2, P, 2, C), torch.float32, y2d.device, "bn_bwd_dual: part"))
     call("sv_bn_bwd_stats_mask_dual", ptr(gm), dt(gm), ptr(act), dt(act), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd),
          ptr(y2), dt(y2), ptr(mean2), ptr(rstd2), rows, C, ptr(part[0]), ptr(part[1]))
     if bn_fold_ok(rows, C, P) and _bn_small_args_ok(gm, y2d, mean, rstd, gamma, y2, mean2, rstd2, gamma2):
-        return _bn_bwd_apply_fold(nv.SV_BN_SMALL_DUAL, gm, y2d, mean, rstd, gamma, part[0], P, part2=part[1], **both)
-    sums = _bn_bwd_sums(P, C, batch_stats, (part[0], dgamma, dbeta), (part[1], dgamma2, dbeta2))
-    dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
-    dx2 = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
+        return _bn_bwd_apply_fold(nv.SV_BN_SMALL_DUAL, gm, y2d, mean, rstd, gamma, part[0], P, part2=part[1], out=o1,
+                                  out2=o2, **both)
+    sums = _bn_bwd_sums(P, C, batch_stats, (part[0], dgamma, dbeta), (part[1], dgamma2, dbeta2), sums=sums)
+    dx = (torch.empty(rows, C, device=y2d.device, dtype=dx_dtype) if o1 is None
+          else _conv_buf(o1, (rows, C), dx_dtype, y2d.device, "bn_bwd_dual: out"))
+    dx2 = (torch.empty(rows, C, device=y2d.device, dtype=dx_dtype) if o2 is None
+           else _conv_buf(o2, (rows, C), dx_dtype, y2d.device, "bn_bwd_dual: out"))
     call("sv_bn_bwd_apply_dual", ptr(gm), dt(gm), ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma), ptr(sums[0]),
          ptr(y2), dt(y2), ptr(mean2), ptr(rstd2), ptr(gamma2), ptr(sums[1]), ptr(dx), ptr(dx2), dt(dx), rows, C)
     return dx, dx2
 
 
 def bn_relu_bwd_pooled(dpool4d: torch.Tensor, idx: torch.Tensor, H: int, W: int, y2d, mean, rstd, gamma, beta, *,
-                       dgamma=None, dbeta=None, dx_dtype=torch.float32, batch_stats: bool = True) -> torch.Tensor:
+                       dgamma=None, dbeta=None, dx_dtype=torch.float32, batch_stats: bool = True,
+                       out: torch.Tensor | None = None, part: torch.Tensor | None = None,
+                       sums: torch.Tensor | None = None) -> torch.Tensor:
     """bn_bwd(maxpool_bwd(dpool, idx, H, W), y, ..., relu_beta=beta) without materialising the max-pool
-    backward: both BatchNorm passes gather it from dpool / idx (sv_bn_relu_bwd_*_pool), bit for bit."""
+    backward: both BatchNorm passes gather it from dpool / idx (sv_bn_relu_bwd_*_pool), bit for bit.
+    ``out`` / ``part`` / ``sums``: the caller's dx, partials and folded sums [1][2][C] buffers (default: fresh)."""
     B, OH, OW, C = dpool4d.shape
     rows = y2d.shape[0]
     _check(dpool4d.dtype in (torch.float32, torch.bfloat16) and dpool4d.is_contiguous() and idx.shape == dpool4d.shape
            and idx.is_contiguous() and (OH, OW) == conv_out_hw(H, W, 3, 2, 1) and rows == B * H * W
            and y2d.shape[1] == C and _bn_c_ok(C), "bn_relu_bwd_pooled: shape mismatch")
     P = value("sv_bn_nparts", rows, C)
-    part = torch.empty(P, 2, C, device=y2d.device, dtype=torch.float32)
+    part = (torch.empty(P, 2, C, device=y2d.device, dtype=torch.float32) if part is None
+            else _conv_buf(part, (P, 2, C), torch.float32, y2d.device, "bn_relu_bwd_pooled: part"))
     call("sv_bn_relu_bwd_stats_pool", ptr(dpool4d), dt(dpool4d), ptr(idx), B, H, W, ptr(y2d), dt(y2d), ptr(mean),
          ptr(rstd), ptr(gamma), ptr(beta), C, ptr(part))
     if (bn_fold_ok(rows, C, P) and rows * C < 2 ** 31
             and _bn_small_args_ok(dpool4d, y2d, mean, rstd, gamma, beta)):
         return _bn_bwd_apply_fold(nv.SV_BN_SMALL_RELU, dpool4d, y2d, mean, rstd, gamma, part, P, idx=idx, H=H, W=W,
-                                  beta=beta, dgamma=dgamma, dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats)
-    sums = _bn_bwd_sums(P, C, batch_stats, (part, dgamma, dbeta))
-    dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
+                                  beta=beta, dgamma=dgamma, dbeta=dbeta, dx_dtype=dx_dtype, batch_stats=batch_stats,
+                                  out=out)
+    sums = _bn_bwd_sums(P, C, batch_stats, (part, dgamma, dbeta), sums=sums)
+    dx = (torch.empty(rows, C, device=y2d.device, dtype=dx_dtype) if out is None
+          else _conv_buf(out, (rows, C), dx_dtype, y2d.device, "bn_relu_bwd_pooled: out"))
     call("sv_bn_relu_bwd_apply_pool", ptr(dpool4d), dt(dpool4d), ptr(idx), B, H, W, ptr(y2d), dt(y2d), ptr(mean),
          ptr(rstd), ptr(gamma), ptr(beta), ptr(sums), ptr(dx), dt(dx), C)
     return dx
@@ -2135,37 +2181,47 @@ def head_loss(logits: torch.Tensor, specs: list) -> tuple:
     return loss, dl
 
 
-def maxpool_fwd(x4d: torch.Tensor):
+def maxpool_fwd(x4d: torch.Tensor, *, out: tuple | None = None):
+    """-> (y, idx uint8: the argmax tap 3 kh + kw); ``out``: the caller's (y, idx) buffers (default: fresh)."""
     B, H, W, C = x4d.shape
     _check(x4d.is_contiguous() and C % 4 == 0, "maxpool_fwd: need contiguous NHWC, C % 4 == 0")
     OH, OW = conv_out_hw(H, W, 3, 2, 1)
-    y = torch.empty(B, OH, OW, C, device=x4d.device, dtype=x4d.dtype)
-    idx = torch.empty(B, OH, OW, C, device=x4d.device, dtype=torch.uint8)
+    if out is None:
+        y = torch.empty(B, OH, OW, C, device=x4d.device, dtype=x4d.dtype)
+        idx = torch.empty(B, OH, OW, C, device=x4d.device, dtype=torch.uint8)
+    else:
+        y = _conv_buf(out[0], (B, OH, OW, C), x4d.dtype, x4d.device, "maxpool_fwd: out")
+        idx = _conv_buf(out[1], (B, OH, OW, C), torch.uint8, x4d.device, "maxpool_fwd: out")
     call("sv_maxpool3s2_fwd", ptr(x4d), dt(x4d), ptr(y), ptr(idx), B, H, W, C)
     return y, idx
 
 
-def maxpool_bwd(dout4d: torch.Tensor, idx: torch.Tensor, H: int, W: int, dx_dtype=torch.float32) -> torch.Tensor:
+def maxpool_bwd(dout4d: torch.Tensor, idx: torch.Tensor, H: int, W: int, dx_dtype=torch.float32, *,
+                out: torch.Tensor | None = None) -> torch.Tensor:
     B, OH, OW, C = dout4d.shape
     _check(dout4d.is_contiguous() and idx.shape == dout4d.shape and (OH, OW) == conv_out_hw(H, W, 3, 2, 1),
            "maxpool_bwd: shape mismatch")
-    dx = torch.empty(B, H, W, C, device=dout4d.device, dtype=dx_dtype)
+    dx = (torch.empty(B, H, W, C, device=dout4d.device, dtype=dx_dtype) if out is None
+          else _conv_buf(out, (B, H, W, C), dx_dtype, dout4d.device, "maxpool_bwd: out"))
     call("sv_maxpool3s2_bwd", ptr(dout4d), dt(dout4d), ptr(idx), ptr(dx), dt(dx), B, H, W, C)
     return dx
 
 
-def avgpool_fwd(x4d: torch.Tensor) -> torch.Tensor:
+def avgpool_fwd(x4d: torch.Tensor, *, out: torch.Tensor | None = None) -> torch.Tensor:
     B, H, W, C = x4d.shape
     _check(x4d.is_contiguous() and C % 4 == 0, "avgpool_fwd: need contiguous NHWC, C % 4 == 0")
-    feat = torch.empty(B, C, device=x4d.device, dtype=torch.float32)
+    feat = (torch.empty(B, C, device=x4d.device, dtype=torch.float32) if out is None
+            else _conv_buf(out, (B, C), torch.float32, x4d.device, "avgpool_fwd: out"))
     call("sv_avgpool_fwd", ptr(x4d), dt(x4d), ptr(feat), B, H * W, C)
     return feat
 
 
-def avgpool_bwd(dfeat: torch.Tensor, shape: tuple, dx_dtype=torch.float32) -> torch.Tensor:
+def avgpool_bwd(dfeat: torch.Tensor, shape: tuple, dx_dtype=torch.float32, *,
+                out: torch.Tensor | None = None) -> torch.Tensor:
     B, H, W, C = shape
     dfeat = dfeat.float().contiguous()
     _check(tuple(dfeat.shape) == (B, C), "avgpool_bwd: dfeat shape")
-    dx = torch.empty(B, H, W, C, device=dfeat.device, dtype=dx_dtype)
+    dx = (torch.empty(B, H, W, C, device=dfeat.device, dtype=dx_dtype) if out is None
+          else _conv_buf(out, (B, H, W, C), dx_dtype, dfeat.device, "avgpool_bwd: out"))
     call("sv_avgpool_bwd", ptr(dfeat), ptr(dx), dt(dx), B, H * W, C)
     return dx
