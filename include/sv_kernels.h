@@ -643,6 +643,59 @@ int sv_attn_stream_bwd(const uint16_t* qkv, const uint16_t* out, const float* ls
                        uint16_t* dqkv, float* dws, int32_t B, int32_t N, int64_t img_rows, int32_t heads,
                        int32_t head_dim, float scale, sv_stream_t stream);
 
+/* ---- Swin: shifted-window attention with a relative-position bias (csrc/swin.hip) ------------------
+ * Replaces timm WindowAttention (SwinTransformerBlock, head dimension 32) together with the block's torch.roll,
+ * window_partition / window_reverse and attention mask, and their autograd backward, between the qkv and proj
+ * Linears, on the layouts those GEMMs store and read (no permute, roll or window copy):
+ *   qkv / dqkv  bf16 [rows][3 * heads * 32]  columns (q|k|v, head, d); rows in image raster order b*H*W + y*W + x
+ *   out / dout  bf16 [rows][heads * 32]
+ *   lse         f32  [B * nW][heads][w*w]     nW = (H/w) * (W/w); window (wy, wx) of image b is b*nW + wy*(W/w) + wx
+ *   bias        f32  [heads][w*w][w*w]        dense (sv_swin_bias_expand), added to the scaled scores
+ * Token (i, j) of window (wy, wx) is the pixel ((wy*w + i + shift) mod H, (wx*w + j + shift) mod W).  The mask is
+ * computed in the kernel from the region of the rolled coordinate (rows [0, H-w) | [H-w, H-shift) | [H-shift, H),
+ * columns likewise): a query / key pair of different regions gets -100 added before the softmax (shift > 0 only).
+ * B, H, W: the batch and the stage's grid, H and W multiples of w; w in [1, 8]; shift in [0, w); rows_total >=
+ * B*H*W rows exist in qkv / out / dout / dqkv: rows [B*H*W, rows_total) are never read and are written as zeros in
+ * `out` (forward) and `dqkv` (backward).  bf16 MFMA with f32 accumulation, f32 softmax with the row max subtracted,
+ * P rounded to bf16 once before P v; the backward recomputes P from lse, D = rowsum(dout . out).  One wave owns a
+ * (window, head)'s dq, dk and dv: no atomics, bitwise reproducible, an image's result independent of the batch.
+ * dbias_part f32 [nparts][heads][w*w][w*w], nparts = sv_winattn_bwd_nparts(B, H, W, w, heads): each wave's sum of
+ * P (dP - D) (unscaled, f32, before dS is rounded) over the windows it walked, every element written;
+ * sv_swin_bias_grad folds them.  head_dim != 32 or w > 8: SV_ERR_UNSUPPORTED before any launch.  qkv / out / dout /
+ * dqkv 16-byte aligned.  scale > 0 (timm: 32^-0.5).                                                             */
+int sv_winattn_bwd_nparts(int32_t B, int32_t H, int32_t W, int32_t w, int32_t heads);
+int sv_winattn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, const float* bias, int32_t B, int32_t H, int32_t W,
+                   int32_t w, int32_t shift, int32_t heads, int32_t head_dim, float scale, int64_t rows_total,
+                   sv_stream_t stream);
+int sv_winattn_bwd(const uint16_t* qkv, const uint16_t* out, const float* lse, const uint16_t* dout, const float* bias,
+                   uint16_t* dqkv, float* dbias_part, int32_t B, int32_t H, int32_t W, int32_t w, int32_t shift,
+                   int32_t heads, int32_t head_dim, float scale, int64_t rows_total, sv_stream_t stream);
+/* dense[h][i][j] = table[index(i, j)][h], index = (yi - yj + w - 1) * (2w - 1) + (xi - xj + w - 1) for tokens
+ * i = yi * w + xi, j = yj * w + xj: timm's relative_position_bias_table [(2w-1)^2][heads] f32 as the attention
+ * kernels read it.  sv_swin_bias_grad: dtable[e][h] (+)= the sum of sum_parts dbias_part[p][h][i][j] over the
+ * (i, j) of index e: the parts of a pair in part order, then the pairs in (yj, xj) order (bitwise reproducible);
+ * accumulate != 0 adds to dtable.                                                                                */
+int sv_swin_bias_expand(const float* table, float* dense, int32_t w, int32_t heads, sv_stream_t stream);
+int sv_swin_bias_grad(const float* dbias_part, float* dtable, int32_t nparts, int32_t w, int32_t heads,
+                      int32_t accumulate, sv_stream_t stream);
+/* timm PatchMerging's gather: y [B*(H/2)*(W/2)][4C] from x [B*H*W][C] (raster rows), the 2x2 neighbourhood
+ * concatenated in the order (h0,w0), (h1,w0), (h0,w1), (h1,w1); sv_patch_merge_bwd is the inverse permutation
+ * (dx [B*H*W][C] from dy): every pixel has one destination, nothing is summed.  H, W: the INPUT grid (even).
+ * dtype SV_F32 or SV_BF16; C * element size a multiple of 16 bytes, pointers 16-byte aligned.  rows_*_total >= the
+ * rows written: the rows beyond them are written as zeros.                                                       */
+int sv_patch_merge(const void* x, void* y, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
+                   int64_t rows_out_total, sv_stream_t stream);
+int sv_patch_merge_bwd(const void* dy, void* dx, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
+                       int64_t rows_in_total, sv_stream_t stream);
+/* stochastic depth (per-sample drop of a residual branch), s f32 [B] with entries 0 or 1 / (1 - p):
+ * out[r][:] = x[r][:] + s[r / rows_per_img] * t[r][:] (f32; out may alias x), and out[r][:] = bf16(s[..] * d[r][:])
+ * (the branch's output gradient).  A row of a dropped sample (s = 0) or beyond B * rows_per_img copies x / is zero
+ * without reading t / d.  C a multiple of 4; 16-byte aligned rows.                                               */
+int sv_rowscale_add(const float* x, const float* t, const float* s, float* out, int64_t rows, int64_t rows_per_img,
+                    int32_t B, int32_t C, sv_stream_t stream);
+int sv_rowscale_cast_bf16(const float* d, const float* s, uint16_t* out, int64_t rows, int64_t rows_per_img, int32_t B,
+                          int32_t C, sv_stream_t stream);
+
 /* ---- ViT / DeiT-III patch embedding operand and token assembly (csrc/vit.hip) --------------------
  * sv_patchify16: the rows of timm PatchEmbed's Conv2d(3, C, 16, stride 16) as a GEMM operand: 768 wide,
  * k = ci * 256 + ky * 16 + kx (proj.weight [C,3,16,16] flattened, so the weight is the B operand as stored), patches

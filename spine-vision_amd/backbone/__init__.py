@@ -2,7 +2,8 @@
 
 from .convnext import CONVNEXT_CFGS, ConvNeXtHip, create_convnext
 from .resnet import RESNET_CFGS, ResNetHip, create_resnet
+from .swin import SWIN_CFGS, SwinHip, create_swin
 from .vit import VIT_CFGS, ViTHip, create_vit
 
 __all__ = ["CONVNEXT_CFGS", "ConvNeXtHip", "create_convnext", "RESNET_CFGS", "ResNetHip", "create_resnet",
-           "VIT_CFGS", "ViTHip", "create_vit"]
+           "SWIN_CFGS", "SwinHip", "create_swin", "VIT_CFGS", "ViTHip", "create_vit"]

@@ -800,6 +800,196 @@ def vit_tokens(pe: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, B: int, P
 
 
 # ----------------------------------------------------------------------------------------------
+# Swin: shifted-window attention with a relative-position bias, patch merging, stochastic depth (csrc/swin.hip)
+# SV_WINATTN=torch: the same maths as torch ops on gathered windows (A/B and parity arm, as SV_ATTN=torch): the rows
+# of every window gathered through an index, matmul -> f32 softmax -> bf16 -> matmul, an explicit backward from the
+# same formulas and a scatter back.  f32 operands (precision="fp32") always take this arm, in f32 throughout.
+WINATTN_TORCH = os.environ.get("SV_WINATTN", "") == "torch"
+WIN_HEAD_DIM = 32
+WIN_MAX = 8
+WIN_MASKED = -100.0
+_WIN_CACHE: dict = {}
+
+
+def window_rows(B: int, H: int, W: int, w: int, shift: int, device) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """(rows int64 [B * nW * w*w], mask f32 [nW, w*w, w*w] or None): the raster row of token (i, j) of window
+    (wy, wx) -- pixel ((wy w + i + shift) mod H, (wx w + j + shift) mod W) -- and timm's shifted-window mask (0 / -100
+    by the region of the rolled coordinate; None when shift = 0).  Cached per geometry."""
+    key = (B, H, W, w, shift, str(device))
+    if key not in _WIN_CACHE:
+        yr = torch.arange(H).view(H // w, 1, w, 1).expand(H // w, W // w, w, w)
+        xr = torch.arange(W).view(1, W // w, 1, w).expand(H // w, W // w, w, w)
+        rows = (((yr + shift) % H) * W + (xr + shift) % W).reshape(1, -1) + (torch.arange(B) * H * W).view(B, 1)
+        mask = None
+        if shift:
+            def reg(v, L):
+                return (v >= L - w).long() + (v >= L - shift).long()
+            lab = (reg(yr, H) * 3 + reg(xr, W)).reshape(-1, w * w)
+            mask = (lab[:, :, None] != lab[:, None, :]).float() * WIN_MASKED
+            mask = mask.to(device)
+        _WIN_CACHE[key] = (rows.reshape(-1).to(device), mask)
+    return _WIN_CACHE[key]
+
+
+def _win_geometry(who: str, qkv, B, H, W, w, shift, heads) -> tuple[int, int]:
+    C = heads * WIN_HEAD_DIM
+    _check(B > 0 and heads > 0 and 1 <= w <= WIN_MAX and 0 <= shift < w and H > 0 and W > 0 and H % w == 0
+           and W % w == 0, f"{who}: need B, heads > 0, 1 <= w <= {WIN_MAX}, 0 <= shift < w and H, W multiples of w")
+    _check(qkv.dim() == 2 and qkv.shape[0] >= B * H * W and qkv.shape[1] == 3 * C and qkv.is_contiguous()
+           and qkv.dtype in (torch.bfloat16, torch.float32),
+           f"{who}: qkv must be contiguous bf16 / f32 [>= {B * H * W}, {3 * C}], got {tuple(qkv.shape)} {qkv.dtype}")
+    return qkv.shape[0], C
+
+
+def _win_torch_arm(qkv, torch_arm) -> bool:
+    return qkv.dtype == torch.float32 or (WINATTN_TORCH if torch_arm is None else bool(torch_arm))
+
+
+def _win_scores(qkv, bias, B, H, W, w, shift, heads, scale):
+    idx, mask = window_rows(B, H, W, w, shift, qkv.device)
+    N = w * w
+    x = qkv[idx].view(-1, N, 3, heads, WIN_HEAD_DIM).permute(2, 0, 3, 1, 4)
+    q, k, v = x[0], x[1], x[2]
+    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale + bias.unsqueeze(0)
+    if mask is not None:
+        s = (s.view(B, -1, heads, N, N) + mask.view(1, -1, 1, N, N)).view(-1, heads, N, N)
+    return idx, q, k, v, s
+
+
+def swin_bias_expand(table: torch.Tensor, w: int) -> torch.Tensor:
+    """timm's relative_position_bias_table [(2w-1)^2, heads] f32 -> the dense bias [heads, w*w, w*w] the window
+    attention reads (sv_swin_bias_expand)."""
+    heads = table.shape[1]
+    _check(table.dim() == 2 and table.shape[0] == (2 * w - 1) ** 2 and table.dtype == torch.float32
+           and table.is_contiguous(), f"swin_bias_expand: table must be contiguous f32 [{(2 * w - 1) ** 2}, heads]")
+    dense = torch.empty(heads, w * w, w * w, device=table.device, dtype=torch.float32)
+    call("sv_swin_bias_expand", ptr(table), ptr(dense), w, heads)
+    return dense
+
+
+def swin_bias_grad(part: torch.Tensor, dtable: torch.Tensor, w: int, accumulate: bool = True) -> torch.Tensor:
+    """dtable [(2w-1)^2, heads] (+)= the partials [nparts, heads, w*w, w*w] of winattn_bwd folded in part order, then
+    over each table entry's (i, j) pairs (sv_swin_bias_grad)."""
+    nparts, heads = part.shape[0], part.shape[1]
+    _check(part.dim() == 4 and tuple(part.shape[2:]) == (w * w, w * w) and part.dtype == torch.float32
+           and part.is_contiguous(), "swin_bias_grad: part must be contiguous f32 [nparts, heads, w*w, w*w]")
+    _check(tuple(dtable.shape) == ((2 * w - 1) ** 2, heads) and dtable.dtype == torch.float32 and dtable.is_contiguous(),
+           "swin_bias_grad: bad dtable")
+    call("sv_swin_bias_grad", ptr(part), ptr(dtable), nparts, w, heads, int(bool(accumulate)))
+    return dtable
+
+
+def winattn_fwd(qkv, bias, B: int, H: int, W: int, w: int, shift: int, heads: int, *, scale: float | None = None,
+                torch_arm: bool | None = None):
+    """(out [rows, heads * 32], lse f32 [B * nW, heads, w*w]) = softmax(scale q k^T + bias + mask) v per (window,
+    head) of qkv [rows, 3 * heads * 32] (rows >= B*H*W in raster order; the rows beyond are not read and zero in
+    ``out``).  bf16 operands run sv_winattn_fwd unless ``torch_arm`` (default: SV_WINATTN=torch); f32 operands always
+    run the torch arm."""
+    rows, C = _win_geometry("winattn_fwd", qkv, B, H, W, w, shift, heads)
+    N = w * w
+    scale = WIN_HEAD_DIM ** -0.5 if scale is None else float(scale)
+    _check(tuple(bias.shape) == (heads, N, N) and bias.dtype == torch.float32 and bias.is_contiguous(),
+           "winattn_fwd: bias must be contiguous f32 [heads, w*w, w*w]")
+    nwin = B * (H // w) * (W // w)
+    if _win_torch_arm(qkv, torch_arm):
+        idx, q, k, v, s = _win_scores(qkv, bias, B, H, W, w, shift, heads, scale)
+        lse = torch.logsumexp(s, dim=-1)
+        p = torch.exp(s - lse.unsqueeze(-1)).to(qkv.dtype)
+        out = torch.zeros(rows, C, device=qkv.device, dtype=qkv.dtype)
+        out[idx] = torch.matmul(p, v).permute(0, 2, 1, 3).reshape(-1, C)
+        return out, lse
+    out = torch.empty(rows, C, device=qkv.device, dtype=qkv.dtype)
+    lse = torch.empty(nwin, heads, N, device=qkv.device, dtype=torch.float32)
+    call("sv_winattn_fwd", ptr(qkv), ptr(out), ptr(lse), ptr(bias), B, H, W, w, shift, heads, WIN_HEAD_DIM, scale, rows)
+    return out, lse
+
+
+def winattn_bwd(qkv, out, lse, dout, bias, B: int, H: int, W: int, w: int, shift: int, heads: int, *,
+                scale: float | None = None, torch_arm: bool | None = None):
+    """(dqkv, dbias_part [nparts, heads, w*w, w*w]) from dout: P recomputed from ``lse``, D = rowsum(dout . out),
+    T = P (dout v^T - D), dv = P^T dout, dS = scale T, dq = dS k, dk = dS^T q; the bias gradient sum_windows T comes as
+    per-wave partials for ``swin_bias_grad`` (one part on the torch arm)."""
+    rows, C = _win_geometry("winattn_bwd", qkv, B, H, W, w, shift, heads)
+    N = w * w
+    scale = WIN_HEAD_DIM ** -0.5 if scale is None else float(scale)
+    nwin = B * (H // w) * (W // w)
+    for name, t_ in (("out", out), ("dout", dout)):
+        _check(tuple(t_.shape) == (rows, C) and t_.is_contiguous() and t_.dtype == qkv.dtype, f"winattn_bwd: bad {name}")
+    _check(tuple(lse.shape) == (nwin, heads, N) and lse.is_contiguous() and lse.dtype == torch.float32,
+           "winattn_bwd: bad lse")
+    _check(tuple(bias.shape) == (heads, N, N) and bias.dtype == torch.float32 and bias.is_contiguous(),
+           "winattn_bwd: bad bias")
+    if _win_torch_arm(qkv, torch_arm):
+        idx, q, k, v, s = _win_scores(qkv, bias, B, H, W, w, shift, heads, scale)
+        o = out[idx].view(-1, N, heads, WIN_HEAD_DIM).permute(0, 2, 1, 3)
+        do = dout[idx].view(-1, N, heads, WIN_HEAD_DIM).permute(0, 2, 1, 3)
+        p = torch.exp(s - lse.unsqueeze(-1))
+        dp = torch.matmul(do.float(), v.float().transpose(-1, -2))
+        t = p * (dp - (do.float() * o.float()).sum(-1, keepdim=True))
+        ds = (t * scale).to(qkv.dtype)
+        g = torch.stack([torch.matmul(ds, k), torch.matmul(ds.transpose(-1, -2), q),
+                         torch.matmul(p.to(qkv.dtype).transpose(-1, -2), do)])  # [3, nwin, heads, N, 32]
+        dqkv = torch.zeros_like(qkv)
+        dqkv[idx] = g.permute(1, 3, 0, 2, 4).reshape(-1, 3 * C)
+        return dqkv, t.sum(0, keepdim=True).contiguous()
+    nparts = value("sv_winattn_bwd_nparts", B, H, W, w, heads)
+    dqkv = torch.empty_like(qkv)
+    part = torch.empty(nparts, heads, N, N, device=qkv.device, dtype=torch.float32)
+    call("sv_winattn_bwd", ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(bias), ptr(dqkv), ptr(part), B, H, W, w, shift,
+         heads, WIN_HEAD_DIM, scale, rows)
+    return dqkv, part
+
+
+def patch_merge(x2d: torch.Tensor, B: int, H: int, W: int, *, rows_out: int | None = None) -> torch.Tensor:
+    """timm PatchMerging's gather (sv_patch_merge): [>= B*H*W, C] -> [rows_out >= B*(H/2)*(W/2), 4C], channel blocks
+    (h0,w0), (h1,w0), (h0,w1), (h1,w1); rows beyond the merged ones are zeros."""
+    C = x2d.shape[1]
+    n = B * (H // 2) * (W // 2)
+    rows_out = n if rows_out is None else int(rows_out)
+    _check(x2d.dim() == 2 and x2d.shape[0] >= B * H * W and x2d.is_contiguous() and H % 2 == 0 and W % 2 == 0
+           and rows_out >= n, "patch_merge: need contiguous [>= B*H*W, C], even H, W and rows_out >= B*H*W/4")
+    y = torch.empty(rows_out, 4 * C, device=x2d.device, dtype=x2d.dtype)
+    call("sv_patch_merge", ptr(x2d), ptr(y), dt(x2d), B, H, W, C, rows_out)
+    return y
+
+
+def patch_merge_bwd(dy2d: torch.Tensor, B: int, H: int, W: int, *, rows_in: int | None = None) -> torch.Tensor:
+    """The inverse permutation of ``patch_merge`` (H, W: the unmerged grid): [>= B*H*W/4, 4C] -> [rows_in, C]."""
+    C = dy2d.shape[1] // 4
+    rows_in = B * H * W if rows_in is None else int(rows_in)
+    _check(dy2d.dim() == 2 and dy2d.shape[1] == 4 * C and dy2d.shape[0] >= B * (H // 2) * (W // 2)
+           and dy2d.is_contiguous() and H % 2 == 0 and W % 2 == 0 and rows_in >= B * H * W, "patch_merge_bwd: bad dy")
+    dx = torch.empty(rows_in, C, device=dy2d.device, dtype=dy2d.dtype)
+    call("sv_patch_merge_bwd", ptr(dy2d), ptr(dx), dt(dy2d), B, H, W, C, rows_in)
+    return dx
+
+
+def _rowscale_check(who: str, x, s, rows_per_img: int) -> None:
+    _check(x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] % 4 == 0
+           and s.dim() == 1 and s.dtype == torch.float32 and s.is_contiguous() and rows_per_img > 0,
+           f"{who}: need contiguous f32 [rows, C % 4 == 0] and an f32 scale vector [B]")
+
+
+def rowscale_add(x: torch.Tensor, t: torch.Tensor, s: torch.Tensor, rows_per_img: int,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """x + s[row // rows_per_img] * t per row (sv_rowscale_add; stochastic depth's residual add).  Rows of a dropped
+    sample (s = 0) and rows beyond the B images copy x."""
+    _rowscale_check("rowscale_add", x, s, rows_per_img)
+    _check(t.shape == x.shape and t.dtype == torch.float32 and t.is_contiguous(), "rowscale_add: bad t")
+    out = torch.empty_like(x) if out is None else out
+    call("sv_rowscale_add", ptr(x), ptr(t), ptr(s), ptr(out), x.shape[0], rows_per_img, s.shape[0], x.shape[1])
+    return out
+
+
+def rowscale_cast_bf16(d: torch.Tensor, s: torch.Tensor, rows_per_img: int) -> torch.Tensor:
+    """bf16(s[row // rows_per_img] * d) per row (sv_rowscale_cast_bf16; the gradient entering a dropped branch)."""
+    _rowscale_check("rowscale_cast_bf16", d, s, rows_per_img)
+    out = torch.empty(d.shape, device=d.device, dtype=torch.bfloat16)
+    call("sv_rowscale_cast_bf16", ptr(d), ptr(s), ptr(out), d.shape[0], rows_per_img, s.shape[0], d.shape[1])
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # Global Response Normalization (ConvNeXt V2, csrc/grn.hip)
 EPS_GRN = 1e-6
 

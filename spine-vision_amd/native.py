@@ -209,6 +209,16 @@ _SIGS = {
     "sv_attn_bwd": [_p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
     "sv_attn_stream_fwd": [_p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
     "sv_attn_stream_bwd": [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f32, _p],
+    # Swin
+    "sv_winattn_bwd_nparts": [_i32, _i32, _i32, _i32, _i32],
+    "sv_winattn_fwd": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _p],
+    "sv_winattn_bwd": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _p],
+    "sv_swin_bias_expand": [_p, _p, _i32, _i32, _p],
+    "sv_swin_bias_grad": [_p, _p, _i32, _i32, _i32, _i32, _p],
+    "sv_patch_merge": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i64, _p],
+    "sv_patch_merge_bwd": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i64, _p],
+    "sv_rowscale_add": [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _p],
+    "sv_rowscale_cast_bf16": [_p, _p, _p, _i64, _i64, _i32, _i32, _p],
     "sv_patchify16": [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i64, _i32, _p],
     "sv_vit_tokens": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_image_to_nhwc": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],

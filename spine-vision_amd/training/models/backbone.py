@@ -9,10 +9,14 @@ for the backbones on the north-star path -- ConvNeXt-tiny/small/base/large and C
 the plain transformers: ViT-tiny/small/base/large (patch 16) and DeiT-III small/base (``deit_tiny`` is the
 reference's alias of deit3_small), their attention on csrc/attn.hip (up to 256 tokens) and csrc/attn_stream.hip (up to 2048); these are
 strict about the image size: one square ``img_size``, a multiple of 16 up to 2048 tokens (224, 256, 384, 512, ...),
-given to ``create`` / ``Classifier`` / ``CoordinateRegressor`` or through env ``SV_VIT_IMG_SIZE`` (default 224).  Every
-other name of the reference registry is recognised (``list_backbones`` returns the reference's full list) but
-raises: those families (Swin, EfficientNet, MobileNet; and ConvNeXt-xlarge, the other ConvNeXt V2 sizes,
-``resnext101``, ``resnet50_d`` and ``resnetrs*``) are outside this build's scope.
+given to ``create`` / ``Classifier`` / ``CoordinateRegressor`` or through env ``SV_VIT_IMG_SIZE`` (default 224) --
+and Swin-small/base (patch 4, window 7, head dimension 32; shifted-window attention with its relative-position bias on
+csrc/swin.hip), strict in the same way: a square ``img_size`` that is a multiple of 224 (window 7) or 256 (window 8),
+from ``create`` / the models or env ``SV_SWIN_IMG_SIZE`` (default 224).  ``swin_tiny`` is built by
+``backbone.swin.create_swin`` but still raises here: an existing test pins that, and lifting the gate is adding the
+name to ``NATIVE``.  Every other name of the reference registry is recognised (``list_backbones`` returns the
+reference's full list) but raises: those families (EfficientNet, MobileNet; and ConvNeXt-xlarge, the other ConvNeXt
+V2 sizes, ``resnext101``, ``resnet50_d`` and ``resnetrs*``) are outside this build's scope.
 ``pretrained=True`` cannot download weights offline; pass ``pretrained=False`` or load a timm
 state_dict with ``load_state_dict`` (keys match).
 """
@@ -62,13 +66,14 @@ BACKBONES: dict[str, str] = {k: v for fam in _FAMILIES.values() for k, v in fam.
 NATIVE = ("convnext_tiny", "convnext_small", "convnext_base", "convnext_large", "convnextv2_base", "convnextv2_large",
           "resnet18", "resnet50", "resnet34", "resnet101", "resnet152", "resnet50_a2", "resnet50_b", "resnet50_c",
           "wide_resnet50", "wide_resnet101", "resnext50",
-          "vit_tiny", "vit_small", "vit_base", "vit_large", "deit_tiny", "deit_small", "deit_base")
+          "vit_tiny", "vit_small", "vit_base", "vit_large", "deit_tiny", "deit_small", "deit_base",
+          "swin_small", "swin_base")
 _FEATURE_DIMS = {"convnext_tiny": 768, "convnext_small": 768, "convnext_base": 1024, "convnext_large": 1536, "convnextv2_base": 1024, "convnextv2_large": 1536,
                  "resnet18": 512, "resnet50": 2048, "resnet34": 512, "resnet101": 2048, "resnet152": 2048,
                  "resnet50_a2": 2048, "resnet50_b": 2048, "resnet50_c": 2048, "wide_resnet50": 2048,
                  "wide_resnet101": 2048, "resnext50": 2048,
                  "vit_tiny": 192, "vit_small": 384, "vit_base": 768, "vit_large": 1024, "deit_tiny": 384,
-                 "deit_small": 384, "deit_base": 768}
+                 "deit_small": 384, "deit_base": 768, "swin_small": 768, "swin_base": 1024}
 
 
 class BackboneFactory:
@@ -78,8 +83,9 @@ class BackboneFactory:
     @classmethod
     def create(cls, name: str, pretrained: bool = True, precision: str | None = None,
                img_size=None) -> tuple[nn.Module, int]:
-        """``img_size`` (an int or a square pair) sizes a ViT / DeiT-III backbone, which is strict about its input
-        size (None: env SV_VIT_IMG_SIZE, else 224); every other family takes any size and ignores it."""
+        """``img_size`` (an int or a square pair) sizes a ViT / DeiT-III or Swin backbone, which are strict about their
+        input size (None: env SV_VIT_IMG_SIZE / SV_SWIN_IMG_SIZE, else 224); every other family takes any size and
+        ignores it."""
         if name not in BACKBONES:
             raise ValueError(f"Unknown backbone: {name}. Available: {', '.join(sorted(BACKBONES))}")
         if name not in NATIVE:
@@ -95,6 +101,10 @@ class BackboneFactory:
             from ...backbone.vit import create_vit
 
             model = create_vit(name, precision=prec, img_size=img_size)
+        elif name.startswith("swin_"):
+            from ...backbone.swin import create_swin
+
+            model = create_swin(name, precision=prec, img_size=img_size)
         else:
             from ...backbone.resnet import create_resnet
 
