@@ -876,6 +876,54 @@ int sv_avgpool_fwd(const void* x, int32_t x_dtype, float* feat, int32_t B, int32
 int sv_avgpool_bwd(const float* dfeat, void* dx, int32_t dx_dtype, int32_t B, int32_t HW, int32_t C,
                    sv_stream_t stream);
 
+/* ---- squeeze-and-excitation and the avg-pool shortcut (csrc/se.hip): ResNet-RS / ResNet-D -------------------
+ * timm Bottleneck with attn_layer=SE: z = bn3(conv3(.)) = gamma (y - mean) rstd + beta over the raw conv output
+ * y [B][HW][C] (f32 or bf16), pooled = mean_hw z, hidden = relu(w1 pooled + b1), gate = sigmoid(w2 hidden + b2),
+ * out = relu(z * gate[b][c] + shortcut).  C a power of two in 16..2048, rd a multiple of 4 up to 2048; every
+ * [B][..] side buffer is f32; all pointers 16-B aligned.  No atomics: every sum has one order (csrc/se.hip), an
+ * image's gate depends on that image's rows alone.
+ *   sv_se_squeeze    part [B][sv_se_nparts(HW, C)][C] = per-image partial channel sums of y (the BatchNorm is
+ *                    affine, so the squeeze never reads z)
+ *   sv_se_excite     folds part, applies the BatchNorm to the mean and runs fc1 / fc2 (w1 [rd][C], w2 [C][rd], torch
+ *                    Conv2d 1x1 layout): ymean = mean_hw y, pooled, hidden (after ReLU) and gate, all kept for backward
+ *   sv_se_join_fwd   out = relu(z * gate + r), r = res or res_gamma (res - res_mean) res_rstd + res_beta
+ *   sv_se_bwd_stats  g = dout * (act > 0) written over dout (the shortcut's gradient), and part [B][nparts][2][C] =
+ *                    per-image partial (sum g, sum g xhat), xhat = (y - mean) rstd
+ *   sv_se_bwd_gate   dgate = gamma sum g xhat + beta sum g -> sigmoid', fc2^T, ReLU mask, fc1^T -> dpool [B][C];
+ *                    dw1 / db1 / dw2 / db2 += (accumulated); with dz = g gate + dpool / HW: sums [2][C] = (sum dz,
+ *                    sum dz xhat) over the batch (zero when batch_stats == 0), dbeta += sum dz, dgamma += sum dz xhat
+ *                    (nullable).  work: 3 B C + B rd floats.
+ *   sv_se_bwd_apply  dy = gamma rstd (dz - sums[0] / n - xhat sums[1] / n), n = B HW
+ * sv_avgpool2x2_*: nn.AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) over NHWC, C % 8 == 0: out
+ * [B][ceil(H/2)][ceil(W/2)][C] = the mean of the 1, 2 or 4 taps inside the image; the backward hands every input
+ * pixel its one window's gradient divided by that window's tap count.
+ * Replaces: timm SEModule / downsample_avg inside resnetrs* / resnet50d (timm/models/resnet.py) + autograd.   */
+int sv_se_nparts(int32_t HW, int32_t C);
+int sv_se_squeeze(const void* y, int32_t y_dtype, float* part, int32_t B, int32_t HW, int32_t C, sv_stream_t stream);
+int sv_se_excite(const float* part, int32_t nparts, const float* mean, const float* rstd, const float* gamma,
+                 const float* beta, const float* w1, const float* b1, const float* w2, const float* b2, float* ymean,
+                 float* pooled, float* hidden, float* gate, int32_t B, int32_t HW, int32_t C, int32_t rd,
+                 sv_stream_t stream);
+int sv_se_join_fwd(const void* y, int32_t y_dtype, const float* mean, const float* rstd, const float* gamma,
+                   const float* beta, const float* gate, const void* res, int32_t res_dtype, const float* res_mean,
+                   const float* res_rstd, const float* res_gamma, const float* res_beta, void* out, int32_t out_dtype,
+                   int32_t B, int32_t HW, int32_t C, sv_stream_t stream);
+int sv_se_bwd_stats(void* dout, int32_t dout_dtype, const void* act, int32_t act_dtype, const void* y, int32_t y_dtype,
+                    const float* mean, const float* rstd, float* part, int32_t B, int32_t HW, int32_t C,
+                    sv_stream_t stream);
+int sv_se_bwd_gate(const float* part, int32_t nparts, const float* ymean, const float* pooled, const float* hidden,
+                   const float* gate, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                   const float* w1, const float* w2, float* work, float* dpool, float* sums, float* dgamma, float* dbeta,
+                   float* dw1, float* db1, float* dw2, float* db2, int32_t batch_stats, int32_t B, int32_t HW, int32_t C,
+                   int32_t rd, sv_stream_t stream);
+int sv_se_bwd_apply(const void* g, int32_t g_dtype, const void* y, int32_t y_dtype, const float* mean,
+                    const float* rstd, const float* gamma, const float* gate, const float* dpool, const float* sums,
+                    void* dx, int32_t dx_dtype, int32_t B, int32_t HW, int32_t C, sv_stream_t stream);
+int sv_avgpool2x2_fwd(const void* x, int32_t dtype, void* y, int32_t B, int32_t H, int32_t W, int32_t C,
+                      sv_stream_t stream);
+int sv_avgpool2x2_bwd(const void* dout, int32_t dout_dtype, void* dx, int32_t dx_dtype, int32_t B, int32_t H, int32_t W,
+                      int32_t C, sv_stream_t stream);
+
 /* ---- classification loss (csrc/loss.hip, ABI v7) ------------------------------------------------
  * The multi-task loss over the fused head's logits [B][K] (f32, row-major) in one launch: loss[0] =
  * sum_k weight_k * loss_k, and dlogits [B][K] = d(loss[0]) / d(logits) (every column of a task's range

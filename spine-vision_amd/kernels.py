@@ -9,6 +9,7 @@ missing library or a CPU tensor raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -2414,4 +2415,189 @@ def avgpool_bwd(dfeat: torch.Tensor, shape: tuple, dx_dtype=torch.float32, *,
     dx = (torch.empty(B, H, W, C, device=dfeat.device, dtype=dx_dtype) if out is None
           else _conv_buf(out, (B, H, W, C), dx_dtype, dfeat.device, "avgpool_bwd: out"))
     call("sv_avgpool_bwd", ptr(dfeat), ptr(dx), dt(dx), B, H * W, C)
+    return dx
+
+
+# ----------------------------------------------------------------------------------------------
+# Squeeze-and-excitation on a bottleneck's last BatchNorm and the avg-pool shortcut (csrc/se.hip): ResNet-RS / -D
+# SV_SE=torch: the same wrappers computed with torch ops on the device (A/B baseline and debugging aid, never the
+# default)
+SE_TORCH = os.environ.get("SV_SE", "") == "torch"
+
+
+def _se_act(who: str, *ts) -> tuple:
+    B, H, W, C = ts[0].shape
+    _check(_is_pow2(C) and 16 <= C <= 2048, f"{who}: C must be a power of two in 16..2048, got {C}")
+    for t in ts:
+        _check(t.is_contiguous() and tuple(t.shape) == (B, H, W, C) and t.dtype in (torch.float32, torch.bfloat16)
+               and t.data_ptr() % 16 == 0, f"{who}: need contiguous 16-B aligned f32 / bf16 [B,H,W,C]={(B, H, W, C)}")
+    return B, H * W, C
+
+
+def _se_f32(who: str, shape: tuple, *ts) -> None:
+    for t in ts:
+        _check(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == math.prod(shape)
+               and t.data_ptr() % 16 == 0, f"{who}: need contiguous 16-B aligned f32 {shape}, got {tuple(t.shape)} {t.dtype}")
+
+
+def _se_out(t, shape: tuple, dtype, device, who: str) -> torch.Tensor:
+    """a fresh output, or the caller's ``out=`` buffer checked (as the BatchNorm wrappers' _conv_buf)"""
+    return torch.empty(shape, device=device, dtype=dtype) if t is None else _conv_buf(t, shape, dtype, device, who)
+
+
+def se_squeeze(y4d: torch.Tensor, *, part: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-image partial channel sums of the raw conv output y [B,H,W,C] -> part [B][P][C] f32 (se_excite folds them).
+    ``part`` / ``out`` / ``work`` of this and the wrappers below: the caller's buffers (default: fresh allocations)."""
+    B, HW, C = _se_act("se_squeeze", y4d)
+    if SE_TORCH:
+        return y4d.float().sum((1, 2)).view(B, 1, C)
+    P = value("sv_se_nparts", HW, C)
+    part = _se_out(part, (B, P, C), torch.float32, y4d.device, "se_squeeze: part")
+    call("sv_se_squeeze", ptr(y4d), dt(y4d), ptr(part), B, HW, C)
+    return part
+
+
+def se_excite(part: torch.Tensor, HW: int, mean, rstd, gamma, beta, w1, b1, w2, b2, *, out: tuple | None = None) -> tuple:
+    """-> (ymean, pooled, hidden, gate): ymean = mean_hw y from the squeeze partials, pooled = its BatchNorm (mean, rstd,
+    gamma, beta), hidden = relu(w1 pooled + b1) [B][rd], gate = sigmoid(w2 hidden + b2) [B][C]; all f32."""
+    B, P, C = part.shape
+    rd = w1.shape[0]
+    _se_f32("se_excite", (B, P, C), part)
+    _se_f32("se_excite", (C,), mean, rstd, gamma, beta, b2)
+    _se_f32("se_excite", (rd,), b1)
+    _se_f32("se_excite", (rd, C), w1, w2)
+    _check(w1.shape[:2] == (rd, C) and w2.shape[:2] == (C, rd) and rd % 4 == 0, "se_excite: w1 [rd,C,1,1], w2 [C,rd,1,1]")
+    if SE_TORCH:
+        ymean = part.sum(1) / HW
+        pooled = (ymean - mean) * rstd * gamma + beta
+        hidden = torch.relu(pooled @ w1.view(rd, C).t() + b1)
+        return ymean, pooled, hidden, torch.sigmoid(hidden @ w2.view(C, rd).t() + b2)
+    o = out if out is not None else (None,) * 4
+    ymean, pooled, gate = (_se_out(t, (B, C), torch.float32, part.device, "se_excite: out") for t in (o[0], o[1], o[3]))
+    hidden = _se_out(o[2], (B, rd), torch.float32, part.device, "se_excite: out")
+    call("sv_se_excite", ptr(part), P, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+         ptr(ymean), ptr(pooled), ptr(hidden), ptr(gate), B, HW, C, rd)
+    return ymean, pooled, hidden, gate
+
+
+def se_join(y4d, mean, rstd, gamma, beta, gate, res, *, res_bn=None, out_dtype=torch.float32, out=None) -> torch.Tensor:
+    """relu((gamma (y - mean) rstd + beta) * gate[b][c] + r), r = res or BN(res) with res_bn = (mean, rstd, gamma, beta)."""
+    B, HW, C = _se_act("se_join", y4d)
+    _check(res.is_contiguous() and tuple(res.shape) == tuple(y4d.shape) and res.data_ptr() % 16 == 0, "se_join: res shape")
+    _se_f32("se_join", (B, C), gate)
+    _se_f32("se_join", (C,), mean, rstd, gamma, beta, *(res_bn or ()))
+    if SE_TORCH:
+        z = ((y4d.float() - mean) * rstd * gamma + beta) * gate.view(B, 1, 1, C)
+        r = res.float()
+        if res_bn is not None:
+            r = (r - res_bn[0]) * res_bn[1] * res_bn[2] + res_bn[3]
+        return torch.relu(z + r).to(out_dtype)
+    rm, rr, rg, rb = res_bn if res_bn is not None else (None, None, None, None)
+    out = _se_out(out, tuple(y4d.shape), out_dtype, y4d.device, "se_join: out")
+    call("sv_se_join_fwd", ptr(y4d), dt(y4d), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(gate), ptr(res), dt(res),
+         ptr(rm), ptr(rr), ptr(rg), ptr(rb), ptr(out), dt(out), B, HW, C)
+    return out
+
+
+def se_bwd_stats(dout4d, act4d, y4d, mean, rstd, *, part: torch.Tensor | None = None) -> torch.Tensor:
+    """Pass A of the backward: dout is OVERWRITTEN with g = dout * (act > 0) (the shortcut's gradient) -> part
+    [B][P][2][C] f32 = per-image partial (sum g, sum g xhat)."""
+    B, HW, C = _se_act("se_bwd_stats", y4d, dout4d, act4d)
+    _se_f32("se_bwd_stats", (C,), mean, rstd)
+    if SE_TORCH:
+        g = dout4d.float() * (act4d > 0)
+        dout4d.copy_(g)
+        g = dout4d.float()
+        xh = (y4d.float() - mean) * rstd
+        return torch.stack((g.sum((1, 2)), (g * xh).sum((1, 2))), 1).view(B, 1, 2, C)
+    P = value("sv_se_nparts", HW, C)
+    part = _se_out(part, (B, P, 2, C), torch.float32, y4d.device, "se_bwd_stats: part")
+    call("sv_se_bwd_stats", ptr(dout4d), dt(dout4d), ptr(act4d), dt(act4d), ptr(y4d), dt(y4d), ptr(mean), ptr(rstd),
+         ptr(part), B, HW, C)
+    return part
+
+
+def se_bwd_gate(part, state: tuple, HW: int, mean, rstd, gamma, beta, w1, w2, *, dw1, db1, dw2, db2, dgamma=None,
+                dbeta=None, batch_stats: bool = True, out: tuple | None = None, work: torch.Tensor | None = None) -> tuple:
+    """The gate's backward from pass A's partials and the forward's ``state`` = (ymean, pooled, hidden, gate):
+    -> (dpool [B][C], sums [2][C]) for se_bwd_apply; dw1 / db1 / dw2 / db2 / dgamma / dbeta accumulate."""
+    ymean, pooled, hidden, gate = state
+    B, P, _, C = part.shape
+    rd = hidden.shape[1]
+    _se_f32("se_bwd_gate", (B, P, 2, C), part)
+    _se_f32("se_bwd_gate", (B, C), ymean, pooled, gate)
+    _se_f32("se_bwd_gate", (B, rd), hidden)
+    _se_f32("se_bwd_gate", (C,), mean, rstd, gamma, beta, db2, *(t for t in (dgamma, dbeta) if t is not None))
+    _se_f32("se_bwd_gate", (rd,), db1)
+    _se_f32("se_bwd_gate", (rd, C), w1, w2, dw1, dw2)
+    if SE_TORCH:
+        sg, sgx = part.sum(1).unbind(1)
+        dsig = (gamma * sgx + beta * sg) * gate * (1 - gate)
+        dh = (dsig @ w2.view(C, rd)) * (hidden > 0)
+        dpool = dh @ w1.view(rd, C)
+        dw2 += (dsig.t() @ hidden).view(dw2.shape)
+        db2 += dsig.sum(0)
+        dw1 += (dh.t() @ pooled).view(dw1.shape)
+        db1 += dh.sum(0)
+        s = torch.stack(((gate * sg + dpool).sum(0), (gate * sgx + dpool * (ymean - mean) * rstd).sum(0)))
+        if dbeta is not None:
+            dbeta += s[0]
+        if dgamma is not None:
+            dgamma += s[1]
+        return dpool, s if batch_stats else torch.zeros_like(s)
+    work = _se_out(work, (3 * B * C + B * rd,), torch.float32, part.device, "se_bwd_gate: work")
+    dpool = _se_out(out[0] if out else None, (B, C), torch.float32, part.device, "se_bwd_gate: out")
+    sums = _se_out(out[1] if out else None, (2, C), torch.float32, part.device, "se_bwd_gate: out")
+    call("sv_se_bwd_gate", ptr(part), P, ptr(ymean), ptr(pooled), ptr(hidden), ptr(gate), ptr(mean), ptr(rstd), ptr(gamma),
+         ptr(beta), ptr(w1), ptr(w2), ptr(work), ptr(dpool), ptr(sums), ptr(dgamma), ptr(dbeta), ptr(dw1), ptr(db1),
+         ptr(dw2), ptr(db2), int(batch_stats), B, HW, C, rd)
+    return dpool, sums
+
+
+def se_bwd_apply(g4d, y4d, mean, rstd, gamma, gate, dpool, sums, *, dx_dtype=torch.float32, out=None) -> torch.Tensor:
+    """Pass B: dy = gamma rstd (g gate + dpool / HW - sums[0] / n - xhat sums[1] / n), n = B HW; g = the masked gradient
+    se_bwd_stats left in dout."""
+    B, HW, C = _se_act("se_bwd_apply", y4d, g4d)
+    _se_f32("se_bwd_apply", (C,), mean, rstd, gamma)
+    _se_f32("se_bwd_apply", (B, C), gate, dpool)
+    _se_f32("se_bwd_apply", (2, C), sums)
+    if SE_TORCH:
+        xh = (y4d.float() - mean) * rstd
+        dz = g4d.float() * gate.view(B, 1, 1, C) + dpool.view(B, 1, 1, C) / HW
+        return (gamma * rstd * (dz - sums[0] / (B * HW) - xh * sums[1] / (B * HW))).to(dx_dtype)
+    dx = _se_out(out, tuple(y4d.shape), dx_dtype, y4d.device, "se_bwd_apply: out")
+    call("sv_se_bwd_apply", ptr(g4d), dt(g4d), ptr(y4d), dt(y4d), ptr(mean), ptr(rstd), ptr(gamma), ptr(gate), ptr(dpool),
+         ptr(sums), ptr(dx), dt(dx), B, HW, C)
+    return dx
+
+
+def _pool2_check(who: str, t: torch.Tensor) -> None:
+    _check(t.dim() == 4 and t.is_contiguous() and t.shape[-1] % 8 == 0 and t.dtype in (torch.float32, torch.bfloat16)
+           and t.data_ptr() % 16 == 0, f"{who}: need contiguous 16-B aligned f32 / bf16 NHWC, C % 8 == 0")
+
+
+def avgpool2x2_fwd(x4d: torch.Tensor, *, out: torch.Tensor | None = None) -> torch.Tensor:
+    """nn.AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) over NHWC -> [B, ceil(H/2), ceil(W/2), C]."""
+    _pool2_check("avgpool2x2_fwd", x4d)
+    B, H, W, C = x4d.shape
+    if SE_TORCH:
+        y = torch.nn.functional.avg_pool2d(x4d.permute(0, 3, 1, 2).float(), 2, 2, ceil_mode=True, count_include_pad=False)
+        return y.permute(0, 2, 3, 1).contiguous().to(x4d.dtype)
+    y = _se_out(out, (B, (H + 1) // 2, (W + 1) // 2, C), x4d.dtype, x4d.device, "avgpool2x2_fwd: out")
+    call("sv_avgpool2x2_fwd", ptr(x4d), dt(x4d), ptr(y), B, H, W, C)
+    return y
+
+
+def avgpool2x2_bwd(dout4d: torch.Tensor, H: int, W: int, dx_dtype=torch.float32, *, out=None) -> torch.Tensor:
+    """-> dx [B,H,W,C]: every input pixel gets its window's gradient divided by the window's tap count (1, 2 or 4)."""
+    _pool2_check("avgpool2x2_bwd", dout4d)
+    B, OH, OW, C = dout4d.shape
+    _check((OH, OW) == ((H + 1) // 2, (W + 1) // 2), "avgpool2x2_bwd: shape mismatch")
+    if SE_TORCH:
+        ones = torch.ones(1, 1, H, W, device=dout4d.device)
+        cnt = torch.nn.functional.avg_pool2d(ones, 2, 2, ceil_mode=True, count_include_pad=False, divisor_override=1)
+        d = (dout4d.float() / cnt.view(1, OH, OW, 1)).repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :H, :W]
+        return d.contiguous().to(dx_dtype)
+    dx = _se_out(out, (B, H, W, C), dx_dtype, dout4d.device, "avgpool2x2_bwd: out")
+    call("sv_avgpool2x2_bwd", ptr(dout4d), dt(dout4d), ptr(dx), dt(dx), B, H, W, C)
     return dx

@@ -255,6 +255,17 @@ _SIGS = {
     "sv_maxpool3s2_bwd": [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_avgpool_fwd": [_p, _i32, _p, _i32, _i32, _i32, _p],
     "sv_avgpool_bwd": [_p, _p, _i32, _i32, _i32, _i32, _p],
+    # ResNet-RS / ResNet-D: squeeze-and-excitation, the avg-pool shortcut
+    "sv_se_nparts": [_i32, _i32],
+    "sv_se_squeeze": [_p, _i32, _p, _i32, _i32, _i32, _p],
+    "sv_se_excite": [_p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
+    "sv_se_join_fwd": [_p, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
+    "sv_se_bwd_stats": [_p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _p],
+    "sv_se_bwd_gate": [_p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                       _i32, _i32, _i32, _p],
+    "sv_se_bwd_apply": [_p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
+    "sv_avgpool2x2_fwd": [_p, _i32, _p, _i32, _i32, _i32, _i32, _p],
+    "sv_avgpool2x2_bwd": [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p],
 }
 _RESTYPES = {"sv_last_error_string": ctypes.c_char_p, "sv_build_target": ctypes.c_char_p,
              "sv_conv_bwd_weight_work_floats": ctypes.c_int64, "sv_gconv_bwd_weight_work_floats": ctypes.c_int64}

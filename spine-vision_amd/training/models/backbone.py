@@ -5,7 +5,8 @@
 Here ``create`` returns the MI355X-native module (HIP kernels, timm module tree and state_dict keys)
 for the backbones on the north-star path -- ConvNeXt-tiny/small/base/large and ConvNeXt V2-base/large
 (localization) and the ResNet family (classification): ResNet-18/34/50/101/152, the ``resnet50_a2`` / ``_b`` /
-``_c`` recipes of ResNet-50, Wide-ResNet-50/101 and ResNeXt-50 (32x4d, its grouped 3x3 on csrc/gconv.hip) -- and
+``_c`` recipes of ResNet-50, Wide-ResNet-50/101, ResNeXt-50 (32x4d, its grouped 3x3 on csrc/gconv.hip) and
+ResNet-RS-101/152 (deep stem, conv stem pool, avg-pool shortcut and squeeze-and-excitation on csrc/se.hip) -- and
 the plain transformers: ViT-tiny/small/base/large (patch 16) and DeiT-III small/base (``deit_tiny`` is the
 reference's alias of deit3_small), their attention on csrc/attn.hip (up to 256 tokens) and csrc/attn_stream.hip (up to 2048); these are
 strict about the image size: one square ``img_size``, a multiple of 16 up to 2048 tokens (224, 256, 384, 512, ...),
@@ -14,9 +15,10 @@ and Swin-small/base (patch 4, window 7, head dimension 32; shifted-window attent
 csrc/swin.hip), strict in the same way: a square ``img_size`` that is a multiple of 224 (window 7) or 256 (window 8),
 from ``create`` / the models or env ``SV_SWIN_IMG_SIZE`` (default 224).  ``swin_tiny`` is built by
 ``backbone.swin.create_swin`` but still raises here: an existing test pins that, and lifting the gate is adding the
-name to ``NATIVE``.  Every other name of the reference registry is recognised (``list_backbones`` returns the
+name to ``NATIVE``; ``resnetrs50`` and ``resnet50_d`` are built by ``backbone.resnet.create_resnet`` and raise here for
+the same reason.  Every other name of the reference registry is recognised (``list_backbones`` returns the
 reference's full list) but raises: those families (EfficientNet, MobileNet; and ConvNeXt-xlarge, the other ConvNeXt
-V2 sizes, ``resnext101``, ``resnet50_d`` and ``resnetrs*``) are outside this build's scope.
+V2 sizes and ``resnext101``) are outside this build's scope.
 ``pretrained=True`` cannot download weights offline; pass ``pretrained=False`` or load a timm
 state_dict with ``load_state_dict`` (keys match).
 """
@@ -65,13 +67,13 @@ BACKBONES: dict[str, str] = {k: v for fam in _FAMILIES.values() for k, v in fam.
 # names built natively on MI355X (the north-star backbones)
 NATIVE = ("convnext_tiny", "convnext_small", "convnext_base", "convnext_large", "convnextv2_base", "convnextv2_large",
           "resnet18", "resnet50", "resnet34", "resnet101", "resnet152", "resnet50_a2", "resnet50_b", "resnet50_c",
-          "wide_resnet50", "wide_resnet101", "resnext50",
+          "wide_resnet50", "wide_resnet101", "resnext50", "resnetrs101", "resnetrs152",
           "vit_tiny", "vit_small", "vit_base", "vit_large", "deit_tiny", "deit_small", "deit_base",
           "swin_small", "swin_base")
 _FEATURE_DIMS = {"convnext_tiny": 768, "convnext_small": 768, "convnext_base": 1024, "convnext_large": 1536, "convnextv2_base": 1024, "convnextv2_large": 1536,
                  "resnet18": 512, "resnet50": 2048, "resnet34": 512, "resnet101": 2048, "resnet152": 2048,
                  "resnet50_a2": 2048, "resnet50_b": 2048, "resnet50_c": 2048, "wide_resnet50": 2048,
-                 "wide_resnet101": 2048, "resnext50": 2048,
+                 "wide_resnet101": 2048, "resnext50": 2048, "resnetrs101": 2048, "resnetrs152": 2048,
                  "vit_tiny": 192, "vit_small": 384, "vit_base": 768, "vit_large": 1024, "deit_tiny": 384,
                  "deit_small": 384, "deit_base": 768, "swin_small": 768, "swin_base": 1024}
 
