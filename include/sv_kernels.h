@@ -924,6 +924,75 @@ int sv_avgpool2x2_fwd(const void* x, int32_t dtype, void* y, int32_t B, int32_t 
 int sv_avgpool2x2_bwd(const void* dout, int32_t dout_dtype, void* dx, int32_t dx_dtype, int32_t B, int32_t H, int32_t W,
                       int32_t C, sv_stream_t stream);
 
+/* ---- MBConv: depthwise 3x3, BatchNorm + SiLU, gating squeeze-and-excitation (csrc/mbconv.hip, ABI v10): EfficientNetV2
+ * timm InvertedResidual between its 1x1 convolutions: a1 = silu(bn1(y1)); y2 = dw3x3(a1); s = silu(bn2(y2));
+ * pooled = mean_hw s, hidden = silu(w1 pooled + b1), gate = sigmoid(w2 hidden + b2); a = s * gate[b][c] is the project
+ * convolution's operand.  NHWC, f32 or bf16 tensors, f32 arithmetic, pre = fmaf(gamma rstd, y - mean, beta) everywhere.
+ * C a multiple of 32 up to 3840, rd a multiple of 4; other shapes return SV_ERR_UNSUPPORTED before any launch.  Every
+ * [B][..] side buffer is f32; all pointers 16-B aligned.  No atomics: every sum has one order (csrc/mbconv.hip), an
+ * image's gate depends on that image's rows alone.  P = sv_mbconv_nparts(rows, C) with rows = the rows one sum runs
+ * over (B HW for the BatchNorm sums, HW for the per-image ones).
+ *   sv_mbconv_bn_stats     part [P][2][C] = (sum y, sum y^2) over all rows: the unshifted partials sv_bn_stats_finish
+ *                          takes with y = NULL (any C % 32 == 0; sv_bn_stats stops at 1024 channels)
+ *   sv_bn_silu_fwd         out = silu(pre) (+ res, nullable, added AFTER the activation: timm ConvBnAct's skip)
+ *   sv_bn_silu_bwd_stats   part [P][2][C] = (sum g, sum g xhat), g = dout silu'(pre), pre recomputed from y as the forward
+ *                          computes it; sv_bn_bwd_finish folds them
+ *   sv_bn_silu_bwd_apply   dx = gamma rstd (g - sums[0] / n - xhat sums[1] / n), n = rows, g recomputed
+ *   sv_mbconv_add          dst += src over n elements (n % 8 == 0), the sum in f32: the identity shortcut's gradient
+ *   sv_dwconv3_fwd         y [B][OH][OW][C] = depthwise 3x3, pad 1, stride 1 | 2, OH = (H - 1) / stride + 1; w = the torch
+ *                          weight [C][1][3][3] f32
+ *   sv_dwconv3_bwd_data    dx [B][H][W][C] from dy [B][OH][OW][C] (odd H, W at stride 2 included)
+ *   sv_dwconv3_bwd_weight  part [sv_dwconv3_bwd_weight_nparts][9][C], folded in part order into dw [C][1][3][3]
+ *                          (accumulate: dw +=)
+ *   sv_mbse_squeeze        part [B][P][C] = per-image partial sums of s
+ *   sv_mbse_excite         folds part -> pooled [B][C]; hpre = w1 pooled + b1, hidden = silu(hpre) [B][rd]; gate [B][C]
+ *                          (w1 [rd][C], w2 [C][rd], torch Conv2d 1x1 layout); all kept for the backward
+ *   sv_mbse_scale          out = s * gate[b][c]
+ *   sv_mbse_bwd_stats      part [B][P][C] = per-image partial sums of da s
+ *   sv_mbse_bwd_gate       dgate = folded part -> sigmoid', w2^T, silu'(hpre), w1^T -> dpool [B][C]; dw1 / db1 / dw2 / db2
+ *                          += (accumulated).  work: B C + B rd floats.
+ *   sv_mbse_bwd_apply      dpre = (da gate + dpool / HW) silu'(pre), stored in dpre_dtype, and part [B P][2][C] = (sum r,
+ *                          sum r xhat) of the stored (rounded) values r: sv_bn_bwd_finish folds them and sv_bn_bwd_apply
+ *                          (act = NULL) finishes bn2's backward
+ * Replaces: timm BatchNormAct2d(SiLU), SqueezeExcite and the depthwise Conv2d of efficientnetv2_* + autograd.       */
+int sv_mbconv_nparts(int64_t rows, int32_t C);
+int sv_mbconv_bn_stats(const void* y, int32_t y_dtype, int64_t rows, int32_t C, float* part, sv_stream_t stream);
+int sv_bn_silu_fwd(const void* y, int32_t y_dtype, const float* mean, const float* rstd, const float* gamma,
+                   const float* beta, const void* res, int32_t res_dtype, void* out, int32_t out_dtype, int64_t rows,
+                   int32_t C, sv_stream_t stream);
+int sv_bn_silu_bwd_stats(const void* dout, int32_t dout_dtype, const void* y, int32_t y_dtype, const float* mean,
+                         const float* rstd, const float* gamma, const float* beta, int64_t rows, int32_t C, float* part,
+                         sv_stream_t stream);
+int sv_bn_silu_bwd_apply(const void* dout, int32_t dout_dtype, const void* y, int32_t y_dtype, const float* mean,
+                         const float* rstd, const float* gamma, const float* beta, const float* sums, void* dx,
+                         int32_t dx_dtype, int64_t rows, int32_t C, sv_stream_t stream);
+int sv_mbconv_add(void* dst, int32_t dst_dtype, const void* src, int32_t src_dtype, int64_t n, sv_stream_t stream);
+int sv_dwconv3_fwd(const void* x, int32_t x_dtype, const float* w, void* y, int32_t y_dtype, int32_t B, int32_t H,
+                   int32_t W, int32_t C, int32_t stride, sv_stream_t stream);
+int sv_dwconv3_bwd_data(const void* dy, int32_t dy_dtype, const float* w, void* dx, int32_t dx_dtype, int32_t B,
+                        int32_t H, int32_t W, int32_t C, int32_t stride, sv_stream_t stream);
+int sv_dwconv3_bwd_weight_nparts(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride);
+int sv_dwconv3_bwd_weight(const void* dy, int32_t dy_dtype, const void* x, int32_t x_dtype, float* part, float* dw,
+                          int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                          sv_stream_t stream);
+int sv_mbse_squeeze(const void* y, int32_t y_dtype, const float* mean, const float* rstd, const float* gamma,
+                    const float* beta, float* part, int32_t B, int32_t HW, int32_t C, sv_stream_t stream);
+int sv_mbse_excite(const float* part, int32_t nparts, const float* w1, const float* b1, const float* w2, const float* b2,
+                   float* pooled, float* hpre, float* hidden, float* gate, int32_t B, int32_t HW, int32_t C, int32_t rd,
+                   sv_stream_t stream);
+int sv_mbse_scale(const void* y, int32_t y_dtype, const float* mean, const float* rstd, const float* gamma,
+                  const float* beta, const float* gate, void* out, int32_t out_dtype, int32_t B, int32_t HW, int32_t C,
+                  sv_stream_t stream);
+int sv_mbse_bwd_stats(const void* da, int32_t da_dtype, const void* y, int32_t y_dtype, const float* mean,
+                      const float* rstd, const float* gamma, const float* beta, float* part, int32_t B, int32_t HW,
+                      int32_t C, sv_stream_t stream);
+int sv_mbse_bwd_gate(const float* part, int32_t nparts, const float* pooled, const float* hpre, const float* hidden,
+                     const float* gate, const float* w1, const float* w2, float* work, float* dpool, float* dw1,
+                     float* db1, float* dw2, float* db2, int32_t B, int32_t C, int32_t rd, sv_stream_t stream);
+int sv_mbse_bwd_apply(const void* da, int32_t da_dtype, const void* y, int32_t y_dtype, const float* mean,
+                      const float* rstd, const float* gamma, const float* beta, const float* gate, const float* dpool,
+                      void* dpre, int32_t dpre_dtype, float* part, int32_t B, int32_t HW, int32_t C, sv_stream_t stream);
+
 /* ---- classification loss (csrc/loss.hip, ABI v7) ------------------------------------------------
  * The multi-task loss over the fused head's logits [B][K] (f32, row-major) in one launch: loss[0] =
  * sum_k weight_k * loss_k, and dlogits [B][K] = d(loss[0]) / d(logits) (every column of a task's range

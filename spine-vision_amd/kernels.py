@@ -2601,3 +2601,297 @@ def avgpool2x2_bwd(dout4d: torch.Tensor, H: int, W: int, dx_dtype=torch.float32,
     dx = _se_out(out, (B, H, W, C), dx_dtype, dout4d.device, "avgpool2x2_bwd: out")
     call("sv_avgpool2x2_bwd", ptr(dout4d), dt(dout4d), ptr(dx), dt(dx), B, H, W, C)
     return dx
+
+
+# ----------------------------------------------------------------------------------------------
+# MBConv (csrc/mbconv.hip): depthwise 3x3, BatchNorm + SiLU and the gating squeeze-and-excitation of EfficientNetV2
+# SV_MBCONV=torch: the same wrappers computed with torch ops on the device, f32 arithmetic and the same rounding points
+# (A/B baseline and debugging aid, never the default)
+MBCONV_TORCH = os.environ.get("SV_MBCONV", "") == "torch"
+MB_MAX_C = 3840
+
+
+def _mb_rows(who: str, C: int, *ts) -> None:
+    _check(C % 32 == 0 and 32 <= C <= MB_MAX_C, f"{who}: C must be a multiple of 32 up to {MB_MAX_C}, got {C}")
+    for t in ts:
+        _check(t.is_contiguous() and t.shape[-1] == C and t.numel() == ts[0].numel()
+               and t.dtype in (torch.float32, torch.bfloat16) and t.data_ptr() % 16 == 0,
+               f"{who}: need contiguous 16-B aligned f32 / bf16 [..., {C}] tensors of one shape")
+
+
+def _mb_bn(who: str, C: int, bn: tuple) -> tuple:
+    """(mean, rstd, gamma, beta) of a BatchNorm, detached and checked"""
+    bn = tuple(t.detach() for t in bn)
+    _check(len(bn) == 4, f"{who}: bn = (mean, rstd, gamma, beta)")
+    _se_f32(who, (C,), *bn)
+    return bn
+
+
+def _mb_pre(y, bn):
+    mean, rstd, gamma, beta = bn
+    return (gamma * rstd) * (y.float() - mean) + beta
+
+
+def _silu_grad(x):
+    s = torch.sigmoid(x)
+    return s * (1 + x * (1 - s))
+
+
+def mbconv_nparts(rows: int, C: int) -> int:
+    return value("sv_mbconv_nparts", rows, C)
+
+
+def mb_bn_stats(y2d: torch.Tensor, *, eps: float = EPS_BN, momentum: float = 0.1, running_mean=None, running_var=None,
+                num_batches_tracked=None):
+    """bn_stats for any C % 32 == 0 (sv_bn_stats stops at 1024 channels): unshifted (sum, sum of squares) partials from
+    csrc/mbconv.hip, folded by the existing sv_bn_stats_finish -> (mean, rstd) f32; running statistics updated."""
+    rows, C = y2d.shape
+    _mb_rows("mb_bn_stats", C, y2d)
+    if MBCONV_TORCH:
+        yf = y2d.float()
+        part = torch.stack((yf.sum(0), (yf * yf).sum(0))).view(1, 2, C).contiguous()
+    else:
+        part = torch.empty(mbconv_nparts(rows, C), 2, C, device=y2d.device, dtype=torch.float32)
+        call("sv_mbconv_bn_stats", ptr(y2d), dt(y2d), rows, C, ptr(part))
+    return bn_stats_from_partials(part, rows, eps=eps, momentum=momentum, running_mean=running_mean,
+                                  running_var=running_var, num_batches_tracked=num_batches_tracked)
+
+
+def bn_silu_fwd(y2d, bn: tuple, *, res=None, out_dtype=torch.float32, out=None) -> torch.Tensor:
+    """silu(gamma (y - mean) rstd + beta) (+ res, added after the activation); bn = (mean, rstd, gamma, beta)."""
+    rows, C = y2d.shape
+    _mb_rows("bn_silu_fwd", C, y2d, *(() if res is None else (res,)))
+    bn = _mb_bn("bn_silu_fwd", C, bn)
+    if MBCONV_TORCH:
+        o = torch.nn.functional.silu(_mb_pre(y2d, bn))
+        return (o if res is None else o + res.float().view(rows, C)).to(out_dtype)
+    out = _se_out(out, (rows, C), out_dtype, y2d.device, "bn_silu_fwd: out")
+    call("sv_bn_silu_fwd", ptr(y2d), dt(y2d), *map(ptr, bn), ptr(res), nv.dt_none(res), ptr(out), dt(out), rows, C)
+    return out
+
+
+def bn_silu_bwd_stats(dout2d, y2d, bn: tuple) -> torch.Tensor:
+    """part [P][2][C] = partial (sum g, sum g xhat), g = dout silu'(pre)."""
+    rows, C = y2d.shape
+    _mb_rows("bn_silu_bwd_stats", C, y2d, dout2d)
+    bn = _mb_bn("bn_silu_bwd_stats", C, bn)
+    if MBCONV_TORCH:
+        g = dout2d.float().view(rows, C) * _silu_grad(_mb_pre(y2d, bn))
+        return torch.stack((g.sum(0), (g * ((y2d.float() - bn[0]) * bn[1])).sum(0))).view(1, 2, C).contiguous()
+    part = torch.empty(mbconv_nparts(rows, C), 2, C, device=y2d.device, dtype=torch.float32)
+    call("sv_bn_silu_bwd_stats", ptr(dout2d), dt(dout2d), ptr(y2d), dt(y2d), *map(ptr, bn), rows, C, ptr(part))
+    return part
+
+
+def bn_silu_bwd_apply(dout2d, y2d, bn: tuple, sums, *, dx_dtype=torch.float32, out=None) -> torch.Tensor:
+    """dx = gamma rstd (g - sums[0] / n - xhat sums[1] / n), g = dout silu'(pre), n = rows."""
+    rows, C = y2d.shape
+    _mb_rows("bn_silu_bwd_apply", C, y2d, dout2d)
+    bn = _mb_bn("bn_silu_bwd_apply", C, bn)
+    _se_f32("bn_silu_bwd_apply", (2, C), sums)
+    if MBCONV_TORCH:
+        g = dout2d.float().view(rows, C) * _silu_grad(_mb_pre(y2d, bn))
+        xh = (y2d.float() - bn[0]) * bn[1]
+        s = sums.view(2, C)
+        return ((bn[2] * bn[1]) * (g - s[0] / rows - xh * s[1] / rows)).to(dx_dtype)
+    dx = _se_out(out, (rows, C), dx_dtype, y2d.device, "bn_silu_bwd_apply: out")
+    call("sv_bn_silu_bwd_apply", ptr(dout2d), dt(dout2d), ptr(y2d), dt(y2d), *map(ptr, bn), ptr(sums), ptr(dx), dt(dx),
+         rows, C)
+    return dx
+
+
+def bn_silu_bwd(dout2d, y2d, bn: tuple, *, dgamma=None, dbeta=None, dx_dtype=torch.float32,
+                batch_stats: bool = True) -> torch.Tensor:
+    """Backward of bn_silu_fwd (without its residual): statistics pass, the existing sv_bn_bwd_finish, apply pass;
+    dgamma / dbeta accumulate."""
+    part = bn_silu_bwd_stats(dout2d, y2d, bn)
+    sums = _bn_bwd_sums(part.shape[0], y2d.shape[1], batch_stats, (part, dgamma, dbeta))
+    return bn_silu_bwd_apply(dout2d, y2d, bn, sums, dx_dtype=dx_dtype)
+
+
+def mb_add(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+    """dst += src (f32 sum, one rounding): the identity shortcut's gradient joining a block's input gradient."""
+    _check(dst.is_contiguous() and src.is_contiguous() and dst.numel() == src.numel() and dst.numel() % 8 == 0,
+           "mb_add: contiguous tensors of one size, a multiple of 8")
+    if MBCONV_TORCH:
+        return dst.copy_(dst.float() + src.float().view(dst.shape))
+    call("sv_mbconv_add", ptr(dst), dt(dst), ptr(src), dt(src), dst.numel())
+    return dst
+
+
+def _dw3_check(who: str, x4d, w, stride: int) -> tuple:
+    B, H, W, C = x4d.shape
+    _mb_rows(who, C, x4d)
+    _check(stride in (1, 2) and tuple(w.shape) == (C, 1, 3, 3) and w.dtype == torch.float32 and w.is_contiguous()
+           and w.data_ptr() % 16 == 0, f"{who}: stride 1 | 2 and a contiguous f32 weight [C,1,3,3]")
+    return B, H, W, C
+
+
+def dwconv3_fwd(x4d: torch.Tensor, w: torch.Tensor, stride: int, *, out_dtype=None, out=None) -> torch.Tensor:
+    """Depthwise 3x3, pad 1 -> [B, (H-1)//stride+1, (W-1)//stride+1, C]."""
+    B, H, W, C = _dw3_check("dwconv3_fwd", x4d, w, stride)
+    out_dtype = out_dtype or x4d.dtype
+    if MBCONV_TORCH:
+        y = torch.nn.functional.conv2d(x4d.float().permute(0, 3, 1, 2), w, stride=stride, padding=1, groups=C)
+        return y.permute(0, 2, 3, 1).contiguous().to(out_dtype)
+    y = _se_out(out, (B, (H - 1) // stride + 1, (W - 1) // stride + 1, C), out_dtype, x4d.device, "dwconv3_fwd: out")
+    call("sv_dwconv3_fwd", ptr(x4d), dt(x4d), ptr(w), ptr(y), dt(y), B, H, W, C, stride)
+    return y
+
+
+def dwconv3_bwd_data(dy4d: torch.Tensor, w: torch.Tensor, H: int, W: int, stride: int, *, dx_dtype=None,
+                     out=None) -> torch.Tensor:
+    B, OH, OW, C = _dw3_check("dwconv3_bwd_data", dy4d, w, stride)
+    _check((OH, OW) == ((H - 1) // stride + 1, (W - 1) // stride + 1), "dwconv3_bwd_data: shape mismatch")
+    dx_dtype = dx_dtype or dy4d.dtype
+    if MBCONV_TORCH:
+        dx = torch.nn.grad.conv2d_input((B, C, H, W), w, dy4d.float().permute(0, 3, 1, 2), stride=stride, padding=1,
+                                        groups=C)
+        return dx.permute(0, 2, 3, 1).contiguous().to(dx_dtype)
+    dx = _se_out(out, (B, H, W, C), dx_dtype, dy4d.device, "dwconv3_bwd_data: out")
+    call("sv_dwconv3_bwd_data", ptr(dy4d), dt(dy4d), ptr(w), ptr(dx), dt(dx), B, H, W, C, stride)
+    return dx
+
+
+def dwconv3_bwd_weight(dy4d: torch.Tensor, x4d: torch.Tensor, stride: int, *, dw: torch.Tensor,
+                       accumulate: bool = True) -> torch.Tensor:
+    """dw [C,1,3,3] f32 (+)= the depthwise weight gradient (per-workgroup partials, folded in part order)."""
+    B, H, W, C = x4d.shape
+    _mb_rows("dwconv3_bwd_weight", C, x4d)
+    _mb_rows("dwconv3_bwd_weight", C, dy4d)
+    _check(stride in (1, 2) and tuple(dy4d.shape) == (B, (H - 1) // stride + 1, (W - 1) // stride + 1, C)
+           and tuple(dw.shape) == (C, 1, 3, 3) and dw.dtype == torch.float32 and dw.is_contiguous(),
+           "dwconv3_bwd_weight: dy [B,OH,OW,C], dw f32 [C,1,3,3]")
+    if MBCONV_TORCH:
+        g = torch.nn.grad.conv2d_weight(x4d.float().permute(0, 3, 1, 2), (C, 1, 3, 3), dy4d.float().permute(0, 3, 1, 2),
+                                        stride=stride, padding=1, groups=C)
+        return dw.add_(g) if accumulate else dw.copy_(g)
+    P = value("sv_dwconv3_bwd_weight_nparts", B, H, W, C, stride)
+    part = torch.empty(P, 9, C, device=x4d.device, dtype=torch.float32)
+    call("sv_dwconv3_bwd_weight", ptr(dy4d), dt(dy4d), ptr(x4d), dt(x4d), ptr(part), ptr(dw), int(accumulate), B, H, W, C,
+         stride)
+    return dw
+
+
+def _mbse_act(who: str, *ts) -> tuple:
+    B, H, W, C = ts[0].shape
+    _mb_rows(who, C, *ts)
+    return B, H * W, C
+
+
+def mbse_squeeze(y4d: torch.Tensor, bn: tuple) -> torch.Tensor:
+    """Per-image partial sums of s = silu(bn(y)) over the raw depthwise output y [B,H,W,C] -> part [B][P][C] f32."""
+    B, HW, C = _mbse_act("mbse_squeeze", y4d)
+    bn = _mb_bn("mbse_squeeze", C, bn)
+    if MBCONV_TORCH:
+        return torch.nn.functional.silu(_mb_pre(y4d, bn)).sum((1, 2)).view(B, 1, C)
+    part = torch.empty(B, mbconv_nparts(HW, C), C, device=y4d.device, dtype=torch.float32)
+    call("sv_mbse_squeeze", ptr(y4d), dt(y4d), *map(ptr, bn), ptr(part), B, HW, C)
+    return part
+
+
+def mbse_excite(part: torch.Tensor, HW: int, w1, b1, w2, b2) -> tuple:
+    """-> (pooled [B][C], hpre [B][rd], hidden = silu(hpre), gate = sigmoid(w2 hidden + b2) [B][C]); all f32."""
+    B, P, C = part.shape
+    rd = w1.shape[0]
+    w1, b1, w2, b2 = (t.detach() for t in (w1, b1, w2, b2))
+    _se_f32("mbse_excite", (B, P, C), part)
+    _se_f32("mbse_excite", (rd, C), w1, w2)
+    _se_f32("mbse_excite", (rd,), b1)
+    _se_f32("mbse_excite", (C,), b2)
+    _check(w1.shape[:2] == (rd, C) and w2.shape[:2] == (C, rd) and rd % 4 == 0, "mbse_excite: w1 [rd,C,1,1], w2 [C,rd,1,1]")
+    if MBCONV_TORCH:
+        pooled = part.sum(1) / HW
+        hpre = pooled @ w1.view(rd, C).t() + b1
+        hidden = torch.nn.functional.silu(hpre)
+        return pooled, hpre, hidden, torch.sigmoid(hidden @ w2.view(C, rd).t() + b2)
+    pooled, gate = (torch.empty(B, C, device=part.device, dtype=torch.float32) for _ in range(2))
+    hpre, hidden = (torch.empty(B, rd, device=part.device, dtype=torch.float32) for _ in range(2))
+    call("sv_mbse_excite", ptr(part), P, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(pooled), ptr(hpre), ptr(hidden), ptr(gate),
+         B, HW, C, rd)
+    return pooled, hpre, hidden, gate
+
+
+def mbse_scale(y4d, bn: tuple, gate, *, out_dtype=torch.float32, out=None) -> torch.Tensor:
+    """a = silu(bn(y)) * gate[b][c]: the project convolution's operand."""
+    B, HW, C = _mbse_act("mbse_scale", y4d)
+    bn = _mb_bn("mbse_scale", C, bn)
+    _se_f32("mbse_scale", (B, C), gate)
+    if MBCONV_TORCH:
+        return (torch.nn.functional.silu(_mb_pre(y4d, bn)) * gate.view(B, 1, 1, C)).to(out_dtype)
+    out = _se_out(out, tuple(y4d.shape), out_dtype, y4d.device, "mbse_scale: out")
+    call("sv_mbse_scale", ptr(y4d), dt(y4d), *map(ptr, bn), ptr(gate), ptr(out), dt(out), B, HW, C)
+    return out
+
+
+def mbse_bwd_stats(da4d, y4d, bn: tuple) -> torch.Tensor:
+    """Backward pass A: part [B][P][C] = per-image partial sums of da * s."""
+    B, HW, C = _mbse_act("mbse_bwd_stats", y4d, da4d)
+    bn = _mb_bn("mbse_bwd_stats", C, bn)
+    if MBCONV_TORCH:
+        return (da4d.float() * torch.nn.functional.silu(_mb_pre(y4d, bn))).sum((1, 2)).view(B, 1, C)
+    part = torch.empty(B, mbconv_nparts(HW, C), C, device=y4d.device, dtype=torch.float32)
+    call("sv_mbse_bwd_stats", ptr(da4d), dt(da4d), ptr(y4d), dt(y4d), *map(ptr, bn), ptr(part), B, HW, C)
+    return part
+
+
+def mbse_bwd_gate(part, state: tuple, w1, w2, *, dw1, db1, dw2, db2) -> torch.Tensor:
+    """The gate's backward from pass A's partials and the forward's ``state`` = (pooled, hpre, hidden, gate) -> dpool
+    [B][C] (the gradient of the SUM's mean: pass B divides by HW); dw1 / db1 / dw2 / db2 accumulate."""
+    pooled, hpre, hidden, gate = state
+    B, P, C = part.shape
+    rd = hidden.shape[1]
+    w1, w2 = w1.detach(), w2.detach()
+    _se_f32("mbse_bwd_gate", (B, P, C), part)
+    _se_f32("mbse_bwd_gate", (B, C), pooled, gate)
+    _se_f32("mbse_bwd_gate", (B, rd), hpre, hidden)
+    _se_f32("mbse_bwd_gate", (rd, C), w1, w2, dw1, dw2)
+    _se_f32("mbse_bwd_gate", (rd,), db1)
+    _se_f32("mbse_bwd_gate", (C,), db2)
+    if MBCONV_TORCH:
+        dsig = part.sum(1) * gate * (1 - gate)
+        dh = (dsig @ w2.view(C, rd)) * _silu_grad(hpre)
+        dpool = dh @ w1.view(rd, C)
+        dw2 += (dsig.t() @ hidden).view(dw2.shape)
+        db2 += dsig.sum(0)
+        dw1 += (dh.t() @ pooled).view(dw1.shape)
+        db1 += dh.sum(0)
+        return dpool
+    work = torch.empty(B * C + B * rd, device=part.device, dtype=torch.float32)
+    dpool = torch.empty(B, C, device=part.device, dtype=torch.float32)
+    call("sv_mbse_bwd_gate", ptr(part), P, ptr(pooled), ptr(hpre), ptr(hidden), ptr(gate), ptr(w1), ptr(w2), ptr(work),
+         ptr(dpool), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), B, C, rd)
+    return dpool
+
+
+def mbse_bwd_apply(da4d, y4d, bn: tuple, gate, dpool, *, out_dtype=torch.float32) -> tuple:
+    """Backward pass B: dpre = (da gate + dpool / HW) silu'(pre) stored in ``out_dtype`` -> (dpre, part [B P][2][C]), the
+    BatchNorm backward partials (sum, sum * xhat) of the stored dpre for bn_bwd(part=...)'s finish and apply."""
+    B, HW, C = _mbse_act("mbse_bwd_apply", y4d, da4d)
+    bn = _mb_bn("mbse_bwd_apply", C, bn)
+    _se_f32("mbse_bwd_apply", (B, C), gate, dpool)
+    if MBCONV_TORCH:
+        dpre = ((da4d.float() * gate.view(B, 1, 1, C) + dpool.view(B, 1, 1, C) / HW) * _silu_grad(_mb_pre(y4d, bn))).to(out_dtype)
+        r = dpre.float()
+        xh = (y4d.float() - bn[0]) * bn[1]
+        return dpre, torch.stack((r.sum((1, 2)), (r * xh).sum((1, 2))), 1).contiguous()
+    P = mbconv_nparts(HW, C)
+    dpre = torch.empty(tuple(y4d.shape), device=y4d.device, dtype=out_dtype)
+    part = torch.empty(B * P, 2, C, device=y4d.device, dtype=torch.float32)
+    call("sv_mbse_bwd_apply", ptr(da4d), dt(da4d), ptr(y4d), dt(y4d), *map(ptr, bn), ptr(gate), ptr(dpool), ptr(dpre),
+         dt(dpre), ptr(part), B, HW, C)
+    return dpre, part
+
+
+def bn_bwd_from_partials(dout2d, y2d, mean, rstd, gamma, part, *, dgamma=None, dbeta=None, dx_dtype=torch.float32,
+                         batch_stats: bool = True) -> torch.Tensor:
+    """An activation-free BatchNorm's backward whose statistics partials [P][2][C] dout's producer already summed
+    (mbse_bwd_apply): the existing sv_bn_bwd_finish and sv_bn_bwd_apply (act = NULL), unchanged."""
+    rows, C = y2d.shape
+    _check(part.dtype == torch.float32 and part.is_contiguous() and tuple(part.shape[1:]) == (2, C),
+           "bn_bwd_from_partials: part must be f32 [P][2][C]")
+    sums = _bn_bwd_sums(part.shape[0], C, batch_stats, (part, dgamma, dbeta))
+    dx = torch.empty(rows, C, device=y2d.device, dtype=dx_dtype)
+    call("sv_bn_bwd_apply", ptr(dout2d), dt(dout2d), None, SV_F32, ptr(y2d), dt(y2d), ptr(mean), ptr(rstd), ptr(gamma),
+         ptr(sums), ptr(dx), dt(dx), None, rows, C)
+    return dx

@@ -266,6 +266,23 @@ _SIGS = {
     "sv_se_bwd_apply": [_p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
     "sv_avgpool2x2_fwd": [_p, _i32, _p, _i32, _i32, _i32, _i32, _p],
     "sv_avgpool2x2_bwd": [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p],
+    # EfficientNetV2: depthwise 3x3, BatchNorm + SiLU, the gating squeeze-and-excitation
+    "sv_mbconv_nparts": [_i64, _i32],
+    "sv_mbconv_bn_stats": [_p, _i32, _i64, _i32, _p, _p],
+    "sv_bn_silu_fwd": [_p, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, _i64, _i32, _p],
+    "sv_bn_silu_bwd_stats": [_p, _i32, _p, _i32, _p, _p, _p, _p, _i64, _i32, _p, _p],
+    "sv_bn_silu_bwd_apply": [_p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _p],
+    "sv_mbconv_add": [_p, _i32, _p, _i32, _i64, _p],
+    "sv_dwconv3_fwd": [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "sv_dwconv3_bwd_data": [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "sv_dwconv3_bwd_weight_nparts": [_i32, _i32, _i32, _i32, _i32],
+    "sv_dwconv3_bwd_weight": [_p, _i32, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "sv_mbse_squeeze": [_p, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
+    "sv_mbse_excite": [_p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
+    "sv_mbse_scale": [_p, _i32, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
+    "sv_mbse_bwd_stats": [_p, _i32, _p, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
+    "sv_mbse_bwd_gate": [_p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
+    "sv_mbse_bwd_apply": [_p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
 }
 _RESTYPES = {"sv_last_error_string": ctypes.c_char_p, "sv_build_target": ctypes.c_char_p,
              "sv_conv_bwd_weight_work_floats": ctypes.c_int64, "sv_gconv_bwd_weight_work_floats": ctypes.c_int64}

@@ -13,12 +13,15 @@ strict about the image size: one square ``img_size``, a multiple of 16 up to 204
 given to ``create`` / ``Classifier`` / ``CoordinateRegressor`` or through env ``SV_VIT_IMG_SIZE`` (default 224) --
 and Swin-small/base (patch 4, window 7, head dimension 32; shifted-window attention with its relative-position bias on
 csrc/swin.hip), strict in the same way: a square ``img_size`` that is a multiple of 224 (window 7) or 256 (window 8),
-from ``create`` / the models or env ``SV_SWIN_IMG_SIZE`` (default 224).  ``swin_tiny`` is built by
+from ``create`` / the models or env ``SV_SWIN_IMG_SIZE`` (default 224) -- and EfficientNetV2-S/M/L (any input size):
+their 1x1 convolutions are GEMMs, the depthwise 3x3, BatchNorm + SiLU and the gating squeeze-and-excitation run on
+csrc/mbconv.hip, and the dense 3x3 convolutions of the first stages go through the ResNet convolution path with the
+channel stride of the tensors they touch padded to a power of two.  ``swin_tiny`` is built by
 ``backbone.swin.create_swin`` but still raises here: an existing test pins that, and lifting the gate is adding the
 name to ``NATIVE``; ``resnetrs50`` and ``resnet50_d`` are built by ``backbone.resnet.create_resnet`` and raise here for
 the same reason.  Every other name of the reference registry is recognised (``list_backbones`` returns the
-reference's full list) but raises: those families (EfficientNet, MobileNet; and ConvNeXt-xlarge, the other ConvNeXt
-V2 sizes and ``resnext101``) are outside this build's scope.
+reference's full list) but raises: those (EfficientNet-B0..B4 and MobileNetV3 -- 5x5 depthwise, hard-swish, widths 16 / 40 /
+112 --; and ConvNeXt-xlarge, the other ConvNeXt V2 sizes and ``resnext101``) are outside this build's scope.
 ``pretrained=True`` cannot download weights offline; pass ``pretrained=False`` or load a timm
 state_dict with ``load_state_dict`` (keys match).
 """
@@ -69,13 +72,14 @@ NATIVE = ("convnext_tiny", "convnext_small", "convnext_base", "convnext_large", 
           "resnet18", "resnet50", "resnet34", "resnet101", "resnet152", "resnet50_a2", "resnet50_b", "resnet50_c",
           "wide_resnet50", "wide_resnet101", "resnext50", "resnetrs101", "resnetrs152",
           "vit_tiny", "vit_small", "vit_base", "vit_large", "deit_tiny", "deit_small", "deit_base",
-          "swin_small", "swin_base")
+          "swin_small", "swin_base", "efficientnetv2_s", "efficientnetv2_m", "efficientnetv2_l")
 _FEATURE_DIMS = {"convnext_tiny": 768, "convnext_small": 768, "convnext_base": 1024, "convnext_large": 1536, "convnextv2_base": 1024, "convnextv2_large": 1536,
                  "resnet18": 512, "resnet50": 2048, "resnet34": 512, "resnet101": 2048, "resnet152": 2048,
                  "resnet50_a2": 2048, "resnet50_b": 2048, "resnet50_c": 2048, "wide_resnet50": 2048,
                  "wide_resnet101": 2048, "resnext50": 2048, "resnetrs101": 2048, "resnetrs152": 2048,
                  "vit_tiny": 192, "vit_small": 384, "vit_base": 768, "vit_large": 1024, "deit_tiny": 384,
-                 "deit_small": 384, "deit_base": 768, "swin_small": 768, "swin_base": 1024}
+                 "deit_small": 384, "deit_base": 768, "swin_small": 768, "swin_base": 1024,
+                 "efficientnetv2_s": 1280, "efficientnetv2_m": 1280, "efficientnetv2_l": 1280}
 
 
 class BackboneFactory:
@@ -107,6 +111,10 @@ class BackboneFactory:
             from ...backbone.swin import create_swin
 
             model = create_swin(name, precision=prec, img_size=img_size)
+        elif name.startswith("efficientnetv2_"):
+            from ...backbone.efficientnet import create_efficientnetv2
+
+            model = create_efficientnetv2(name, precision=prec)
         else:
             from ...backbone.resnet import create_resnet
 
