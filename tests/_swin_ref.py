@@ -11,7 +11,11 @@ autograd-differentiable on the CPU in fp32 or float64, and it is written as timm
 1 / (1 - p) (the hook the HIP module has too).
 
 ``winattn_f64`` is float64 windowed attention over raster rows with autograd; ``winattn_restated`` the same rounding to
-bf16 exactly where the kernels do (the rule of tests/test_attn_gpu.py)."""
+bf16 exactly where the kernels do (the rule of tests/test_attn_gpu.py).  The last section states each window-attention
+call alone in float64 with a per-element error bound, and in float32 with faults that can be switched on
+(tests/test_swin_calls_gpu.py, tests/test_swin_calls_cpu.py)."""
+import functools
+
 import torch
 import torch.nn as nn
 
@@ -392,3 +396,297 @@ def block_restated(blk, x, d, *, rows, slab_split=None, s1=None, s2=None, rounde
     g["attn.qkv.weight"], g["attn.qkv.bias"] = wgrad(dqkv, y1), dqkv.sum(0)
     ddx, g["norm1.weight"], g["norm1.bias"] = _ln64_bwd(dqkv @ wq, xh1, rs1, p["norm1.weight"])
     return dict(out=out.reshape(B, H, W, C), dx=(d + ddx).reshape(B, H, W, C), grads=g)
+
+
+# ---- the window-attention calls one at a time: float64 references, per-element bounds and a float32 restatement
+# (tests/test_swin_calls_gpu.py derives every term of the bounds in its docstring; tests/test_swin_calls_cpu.py checks
+# the bounds against the restatement and against faults put into it)
+U32 = 2.0 ** -24  # unit roundoff of f32 (round to nearest)
+U16 = 2.0 ** -8  # unit roundoff of bf16
+TINY = 2.0 ** -126  # smallest normal f32 / bf16: what a flushed denormal loses
+EXP2_REL = 2.0 ** -21  # relative error granted to the hardware exp2 (documented at 1 ulp = 2^-23; four times that)
+LSE_ABS = 1e-3  # the project's bound on lse (the fast log's accuracy cannot be read from the code)
+WAVE_TARGET = 1024
+FAULTS = ("dropped_key", "mask_unrolled", "bias_transposed", "shift_sign", "skip_round2", "db_reset", "lse_by_part",
+          "no_max", "d_unrounded")
+
+
+def f32_scale(scale):
+    """the scale as the entry points receive it (a C float)"""
+    return float(torch.tensor(scale, dtype=torch.float32))
+
+
+def win_nparts(B, H, W, w, heads):
+    """csrc/swin.hip's win_nparts restated: the waves of one head"""
+    return max(1, min(max(1, WAVE_TARGET // heads), B * (H // w) * (W // w)))
+
+
+def walk_depths(total, nparts):
+    """how many windows the waves part = 0 .. nparts-1 walk: the set of depths"""
+    return {len(range(p, total, nparts)) for p in range(nparts)}
+
+
+def calls_inputs(geom, variant="uniform"):
+    """qkv, dout (bf16-exact float64) and the f32-exact table of tests/test_winattn_gpu.py's recipe: q, k in
+    [-1.5, 1.5], v and dout in [-1, 1], table in [-2, 2] (16 for ``table16``), q[..., 0] = 24 and k[..., 0] = +-24 for
+    ``shift_up`` / ``shift_down``; independent draws per row, so every window and head has its own data."""
+    B, H, W, w, shift, heads = geom
+    g = torch.Generator().manual_seed(15485863 + 104729 * B + 7919 * H + 131 * W + 17 * w + 5 * shift + heads)
+    C, n = heads * 32, B * H * W
+    qkv = torch.rand(n, 3 * C, generator=g, dtype=torch.float64) * 2 - 1
+    qkv.view(n, 3, C)[:, :2] *= 1.5
+    if variant.startswith("shift"):
+        qk = qkv.view(n, 3, heads, 32)
+        qk[:, 0, :, 0] = 24.0
+        qk[:, 1, :, 0] = 24.0 if variant == "shift_up" else -24.0
+    qkv = _bf(qkv)
+    dout = _bf(torch.rand(n, C, generator=g, dtype=torch.float64) * 2 - 1)
+    amp = 16.0 if variant == "table16" else 2.0
+    table = ((torch.rand((2 * w - 1) ** 2, heads, generator=g, dtype=torch.float64) * 2 - 1) * amp).float().double()
+    return qkv, dout, table
+
+
+def _gather1(x, B, H, W, w, shift, heads):  # raster [rows, heads * 32] -> [B * nW, heads, N, 32]
+    x = x[:B * H * W].view(B, H, W, heads * 32)
+    x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2)) if shift else x
+    return window_partition(x, w).view(-1, w * w, heads, 32).permute(0, 2, 1, 3)
+
+
+def score_bound(absdot, scaled, *, head_dim, biased=None, masked=None):
+    """|error| of a score: a head_dim-term f32 MFMA sum of exact bf16 products (``absdot`` = scale sum_d |q_d||k_d|),
+    one rounding of the product with the scale or of the fma with the bias (``biased`` = scale q.k + bias; None: no
+    bias term), one of the addition of the mask (``masked``; None: no mask added)."""
+    e = head_dim * U32 * absdot + U32 * (scaled if biased is None else biased).abs()
+    return e if masked is None else e + U32 * masked.abs()
+
+
+def _scores_dense(q, k, bias, geom, scale):
+    """float64 scores [B * nW, heads, N, N] from the dense bias, and their error bound"""
+    B, H, W, w, shift, heads = geom
+    N = w * w
+    scaled = (q @ k.transpose(-1, -2)) * scale
+    absdot = (q.abs() @ k.abs().transpose(-1, -2)) * scale
+    s0 = scaled + bias.unsqueeze(0)
+    m = attn_mask(H, W, w, shift)
+    if m is None:
+        return s0, score_bound(absdot, scaled, head_dim=q.shape[-1], biased=s0)
+    s = (s0.view(B, -1, heads, N, N) + m.double().view(1, -1, 1, N, N)).view(-1, heads, N, N)
+    return s, score_bound(absdot, scaled, head_dim=q.shape[-1], biased=s0, masked=s)
+
+
+def stored_bf16(ref, err):
+    """the bound of a value computed within ``err`` and then stored as bf16"""
+    return err + U16 * (ref.abs() + err) + TINY
+
+
+def softmax_out_bound(p, v, out, ds, arg, nkeys):
+    """|error| of out = (sum_k bf16(e_k) v_k) / l before its store, e_k = exp2((s_k - m) log2 e), l = sum_k e_k in f32.
+    ``arg`` = s - m.  The max m is common to the row and cancels in e / l."""
+    pv = p @ v.abs()
+    dmax = (ds + 3 * U32 * arg.abs()).max(-1, keepdim=True).values + EXP2_REL  # relative error of an e_k, row maximum
+    return (U16 + 2 * dmax + 2 * nkeys * U32) * pv + 3 * U32 * out.abs()
+
+
+def winattn_fwd_ref(qkv, bias, geom, scale):
+    """float64 of sv_winattn_fwd on its operands -> dict(out, out_bound [B*H*W, C] raster; lse [B * nW, heads, N])"""
+    B, H, W, w, shift, heads = geom
+    q, k, v = _gather(qkv.double(), B, H, W, w, shift, heads)
+    s, ds = _scores_dense(q, k, bias.double(), geom, scale)
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    out = p @ v
+    err = softmax_out_bound(p, v, out, ds, s - s.max(-1, keepdim=True).values, w * w)
+    return dict(out=_scatter(out, B, H, W, w, shift), out_bound=_scatter(stored_bf16(out, err), B, H, W, w, shift),
+                lse=lse)
+
+
+def winattn_bwd_ref(qkv, out, lse, dout, bias, geom, scale, nparts):
+    """float64 of sv_winattn_bwd on its operands (``out`` bf16 and ``lse`` f32 are operands: D = rowsum(dout . out),
+    P = exp(score - lse)) -> dict(dqkv, dqkv_bound raster; part, part_bound [nparts, heads, N, N], part p the sum
+    of T over the windows p, p + nparts, ...; tsum / tabs [heads, N, N], the sums of T and of |T| over all windows)."""
+    B, H, W, w, shift, heads = geom
+    N, hd = w * w, 32
+    q, k, v = _gather(qkv.double(), B, H, W, w, shift, heads)
+    do, o = (_gather1(t.double(), B, H, W, w, shift, heads) for t in (dout, out))
+    s, ds = _scores_dense(q, k, bias.double(), geom, scale)
+    arg = s - lse.double().unsqueeze(-1)
+    p = torch.exp(arg)
+    ep = p * (ds + 3 * U32 * arg.abs() + EXP2_REL) + TINY  # score, the argument's subtraction and product, exp2
+    del s, ds, arg
+    g = do @ v.transpose(-1, -2) - (do * o).sum(-1, keepdim=True)  # dP - D
+    eg = hd * U32 * (do.abs() @ v.abs().transpose(-1, -2) + (do.abs() * o.abs()).sum(-1, keepdim=True))
+    t = p * g
+    et = ep * g.abs() + p * eg + 2 * U32 * t.abs() + TINY  # P's error, dP's and D's sums, the subtraction, the product
+    del g, eg
+    dS = t * scale
+    edS = (scale * et + U32 * dS.abs()) * (1 + U16) + U16 * dS.abs() + TINY  # the product with scale, then bf16
+    epb = ep * (1 + U16) + U16 * p  # P as a bf16 MFMA operand
+    del ep
+    acc = N * U32  # f32 accumulation over the N tokens of the window
+    dq, edq = dS @ k, edS @ k.abs() + acc * (dS.abs() @ k.abs())
+    dk, edk = dS.transpose(-1, -2) @ q, edS.transpose(-1, -2) @ q.abs() + acc * (dS.abs().transpose(-1, -2) @ q.abs())
+    dv, edv = p.transpose(-1, -2) @ do, epb.transpose(-1, -2) @ do.abs() + acc * (p.transpose(-1, -2) @ do.abs())
+    del dS, edS, epb, p
+    dqkv = torch.cat([_scatter(x, B, H, W, w, shift) for x in (dq, dk, dv)], dim=1)
+    bound = torch.cat([_scatter(stored_bf16(x, e), B, H, W, w, shift) for x, e in ((dq, edq), (dk, edk), (dv, edv))], dim=1)
+    total = t.shape[0]
+    part = torch.zeros(nparts, heads, N, N, dtype=torch.float64)
+    pe, pa = torch.zeros_like(part), torch.zeros_like(part)
+    depth = torch.zeros(nparts, 1, 1, 1, dtype=torch.float64)
+    for first in range(0, total, nparts):  # round r of the walk: windows r * nparts + p
+        m = min(nparts, total - first)
+        part[:m] += t[first:first + m]
+        pe[:m] += et[first:first + m]
+        pa[:m] += t[first:first + m].abs()
+        depth[:m] += 1
+    return dict(dqkv=dqkv, dqkv_bound=bound, part=part, part_bound=pe + depth * U32 * pa,  # one f32 addition per window
+                tsum=t.sum(0), tabs=t.abs().sum(0))
+
+
+def _to_table(x, w):  # [heads, N, N] -> [(2w-1)^2, heads]: every table entry's sum over its (i, j) pairs
+    heads = x.shape[0]
+    return torch.zeros((2 * w - 1) ** 2, heads, dtype=x.dtype).index_add_(
+        0, relative_position_index(w).view(-1), x.permute(1, 2, 0).reshape(w ** 4, heads))
+
+
+def bias_grad_ref(part, prior, w, accumulate):
+    """float64 of sv_swin_bias_grad on its operands -> (dtable, bound): nparts additions per lane, up to w*w in lane
+    order, then the prior"""
+    nparts = part.shape[0]
+    t = _to_table(part.double().sum(0), w)
+    ref = t + prior.double() if accumulate else t
+    bound = (nparts + w * w) * U32 * _to_table(part.double().abs().sum(0), w)
+    return ref, bound + (U32 * ref.abs() if accumulate else 0.0) + TINY
+
+
+def dtable_chain_ref(b, prior, w, nparts):
+    """dtable = prior + sum over all windows and pairs of T, from winattn_bwd_ref's dict: the bounds of the partials
+    (the terms' own and one addition per window of the walk), then nparts additions per lane, w*w in lane order and
+    the prior"""
+    ref = _to_table(b["tsum"], w) + prior.double()
+    return ref, _to_table(b["part_bound"].sum(0) + (nparts + w * w) * U32 * b["tabs"], w) + U32 * ref.abs() + TINY
+
+
+def ratio(got, ref, bound):
+    """|got - ref| / bound per element, inf where got is not finite"""
+    r = (got.double() - ref).abs() / bound
+    return torch.where(torch.isfinite(got.double()), r, torch.full_like(r, float("inf")))
+
+
+# the float32 restatement: the kernels' index formula, the kernels' rounding points, torch's summation orders
+def walk_index(B, H, W, w, shift, *, sign=1, unrolled_labels=False):
+    """(rows [B * nW, N], labels [B * nW, N]) by the kernels' formula; ``sign`` = -1 and ``unrolled_labels`` are
+    the faults 'shift sign flipped' and 'mask regions from the unrolled coordinate'"""
+    nwy, nwx, N = H // w, W // w, w * w
+    yr = (torch.arange(nwy).view(-1, 1, 1, 1) * w + torch.arange(w).view(1, 1, -1, 1)).expand(nwy, nwx, w, w)
+    xr = (torch.arange(nwx).view(1, -1, 1, 1) * w + torch.arange(w).view(1, 1, 1, -1)).expand(nwy, nwx, w, w)
+    y, x = (yr + sign * shift) % H, (xr + sign * shift) % W
+    rows = ((y * W + x).reshape(1, -1, N) + (torch.arange(B) * H * W).view(B, 1, 1)).reshape(-1, N)
+
+    def reg(v, L):
+        return (v >= L - w).long() + (v >= L - shift).long()
+
+    ly, lx = (y, x) if unrolled_labels else (yr, xr)
+    lab = (reg(ly, H) * 3 + reg(lx, W)).reshape(1, -1, N).expand(B, -1, -1).reshape(-1, N)
+    return rows, (lab if shift else torch.zeros_like(lab))
+
+
+def _restated_scores(qkv, bias, geom, scale, fault):
+    B, H, W, w, shift, heads = geom
+    N = w * w
+    rows, lab = walk_index(B, H, W, w, shift, sign=-1 if fault == "shift_sign" else 1,
+                           unrolled_labels=fault == "mask_unrolled")
+    x = qkv.float()[rows].view(-1, N, 3, heads, 32).permute(2, 0, 3, 1, 4)
+    q, k, v = x[0], x[1], x[2]
+    b = bias.float()
+    b = b.transpose(-1, -2) if fault == "bias_transposed" else b
+    s = (q @ k.transpose(-1, -2)) * torch.tensor(scale, dtype=torch.float32) + b.unsqueeze(0)
+    masked = (lab[:, :, None] != lab[:, None, :]).unsqueeze(1)
+    return rows, q, k, v, torch.where(masked, s + MASKED, s)
+
+
+def _done(total, nparts, fault):
+    return min(total, nparts) if fault == "skip_round2" else total
+
+
+def winattn_fwd_restated32(qkv, bias, geom, scale, nparts, fault=None):
+    """-> (out [B*H*W, C] of bf16 values, lse [B * nW, heads, N] of f32 values), NaN where nothing was written"""
+    B, H, W, w, shift, heads = geom
+    N, C = w * w, heads * 32
+    rows, q, k, v, s = _restated_scores(qkv, bias, geom, scale, fault)
+    m = torch.zeros_like(s[..., :1]) if fault == "no_max" else s.max(-1, keepdim=True).values
+    e = torch.exp(s - m)
+    if fault == "dropped_key":
+        e[..., N - 1] = 0
+    l = e.sum(-1, keepdim=True)
+    o = ((e.bfloat16().float() @ v) * (1.0 / l)).bfloat16().float()
+    lse = (m + torch.log(l)).squeeze(-1)
+    total = rows.shape[0]
+    done = _done(total, nparts, fault)
+    out = torch.full((B * H * W, C), float("nan"))
+    out[rows[:done].reshape(-1)] = o[:done].permute(0, 2, 1, 3).reshape(-1, C)
+    lse_out = torch.full_like(lse, float("nan"))
+    if fault == "lse_by_part":
+        for first in range(0, total, nparts):
+            mm = min(nparts, total - first)
+            lse_out[:mm] = lse[first:first + mm]
+    else:
+        lse_out[:done] = lse[:done]
+    return out.double(), lse_out.double()
+
+
+def winattn_bwd_restated32(qkv, out, lse, dout, bias, geom, scale, nparts, fault=None, out_unrounded=None):
+    """-> (dqkv [B*H*W, 3C] of bf16 values, part [nparts, heads, N, N] of f32 values)"""
+    B, H, W, w, shift, heads = geom
+    N, C = w * w, heads * 32
+    rows, q, k, v, s = _restated_scores(qkv, bias, geom, scale, fault)
+    total = rows.shape[0]
+
+    def win(x):
+        return x.float()[rows].view(-1, N, heads, 32).permute(0, 2, 1, 3)
+
+    do, o = win(dout), win(out_unrounded if fault == "d_unrounded" else out)
+    ls = lse.float()
+    ls = ls[torch.arange(total) % nparts] if fault == "lse_by_part" else ls
+    p = torch.exp(s - ls.unsqueeze(-1))
+    if fault == "dropped_key":
+        p[..., N - 1] = 0
+    t = p * (do @ v.transpose(-1, -2) - (do * o).sum(-1, keepdim=True))
+    dS = (t * torch.tensor(scale, dtype=torch.float32)).bfloat16().float()
+    g = torch.stack([(dS @ k), (dS.transpose(-1, -2) @ q), (p.bfloat16().float().transpose(-1, -2) @ do)])
+    g = g.bfloat16().float()  # [3, B * nW, heads, N, 32]
+    done = _done(total, nparts, fault)
+    dqkv = torch.full((B * H * W, 3 * C), float("nan"))
+    dqkv[rows[:done].reshape(-1)] = g[:, :done].permute(1, 3, 0, 2, 4).reshape(-1, 3 * C)
+    part = torch.zeros(nparts, heads, N, N)
+    for first in range(0, done, nparts):
+        mm = min(nparts, total - first)
+        if fault == "db_reset":
+            part[:mm] = t[first:first + mm]
+        else:
+            part[:mm] += t[first:first + mm]
+    return dqkv.double(), part.double()
+
+
+def bias_grad_restated32(part, prior, w, accumulate):
+    t = _to_table(part.float().sum(0), w)
+    return (t + prior.float() if accumulate else t).double()
+
+
+@functools.lru_cache(maxsize=None)
+def calls_case(geom, variant="uniform", scale=32 ** -0.5):
+    """Operands, float64 references and bounds of the three calls, the backward's on CPU-made operands (the float64
+    forward rounded to bf16 / f32) and a non-zero prior of dtable; computed once per case, shared by the tests of
+    both files, never modified."""
+    B, H, W, w, shift, heads = geom
+    scale = f32_scale(scale)
+    qkv, dout, table = calls_inputs(geom, variant)
+    bias = dense_bias(table, w).contiguous()
+    nparts = win_nparts(B, H, W, w, heads)
+    f = winattn_fwd_ref(qkv, bias, geom, scale)
+    out, lse = _bf(f["out"]), f["lse"].float().double()
+    g = torch.Generator().manual_seed(heads)
+    prior = (torch.rand(table.shape, generator=g) * 2 - 1).double()
+    b = winattn_bwd_ref(qkv, out, lse, dout, bias, geom, scale, nparts)
+    return dict(qkv=qkv, dout=dout, table=table, bias=bias, nparts=nparts, scale=scale, fwd=f, out=out, lse=lse,
+                prior=prior, bwd=b, dtable=dtable_chain_ref(b, prior, w, nparts))
