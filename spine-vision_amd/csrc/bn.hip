@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "chanvec.h"
 #include "common.h"
 
 namespace sv {
@@ -18,17 +19,6 @@ namespace bn {
 
 constexpr int kThreads = 256;
 
-template <typename T>
-__device__ __forceinline__ float4 ld4t(const void* p, size_t i) {
-  return ld4(reinterpret_cast<const T*>(p), i);
-}
-__device__ __forceinline__ float4 ld4d(const void* p, int dt, size_t i) {
-  return dt == SV_F32 ? ld4t<float>(p, i) : ld4t<uint16_t>(p, i);
-}
-__device__ __forceinline__ void st4d(void* p, int dt, size_t i, float4 v) {
-  if (dt == SV_F32) st4(reinterpret_cast<float*>(p), i, v);
-  else st4(reinterpret_cast<uint16_t*>(p), i, v);
-}
 __device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
 // channel of flat element e: 32-bit division where the tensor fits (64-bit division is a long software sequence
 // on the GPU and these passes run it once per element group); `n` = the tensor's element count
@@ -37,44 +27,6 @@ __device__ __forceinline__ int chan_of(size_t e, int C, int64_t n) {
 }
 __device__ __forceinline__ float4 ld4f(const float* p, int c) { return *reinterpret_cast<const float4*>(p + c); }
 
-// V consecutive channels per thread: 8 (one 16-B bf16 access, two 16-B f32 accesses) when C % 8 == 0,
-// else 4.  Per-channel parameters are read as float4s from L1/L2.
-template <int V>
-__device__ __forceinline__ void ldv(const void* p, int dt, size_t i, float (&o)[V]) {
-  if constexpr (V == 8) {
-    if (dt == SV_F32) {
-      const float* f = reinterpret_cast<const float*>(p) + i;
-      const float4 a = *reinterpret_cast<const float4*>(f), b = *reinterpret_cast<const float4*>(f + 4);
-      o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    } else {
-      const uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(p) + i);
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        o[2 * k] = __uint_as_float(w[k] << 16);
-        o[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-      }
-    }
-  } else {
-    const float4 a = ld4d(p, dt, i);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-  }
-}
-template <int V>
-__device__ __forceinline__ void stv(void* p, int dt, size_t i, const float (&v)[V]) {
-  if constexpr (V == 8) {
-    if (dt == SV_F32) {
-      float* f = reinterpret_cast<float*>(p) + i;
-      *reinterpret_cast<float4*>(f) = make_float4(v[0], v[1], v[2], v[3]);
-      *reinterpret_cast<float4*>(f + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-      *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p) + i) =
-          make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-    }
-  } else {
-    st4d(p, dt, i, make_float4(v[0], v[1], v[2], v[3]));
-  }
-}
 // the elementwise forms every pass shares (so the one-launch small-row kernels at the end of this file give
 // the multi-launch path's bits): the affine pre-activation and the train-mode data gradient, every fused
 // multiply-add written out -- hipcc contracts a*b+c by context (a product hoisted out of a loop or shared by two
@@ -86,15 +38,8 @@ __device__ __forceinline__ float bn_dx(float ga, float rs, float g, float sg, fl
   return (ga * rs) * fmaf(-xs, inv_n, a1);              // gamma rstd (g - sum g / n - xhat sum g xhat / n)
 }
 
-template <int V>
-__device__ __forceinline__ void ldp(const float* p, int c, float (&o)[V]) {
-#pragma unroll
-  for (int k = 0; k < V; k += 4) {
-    const float4 a = *reinterpret_cast<const float4*>(p + c + k);
-    o[k] = a.x; o[k + 1] = a.y; o[k + 2] = a.z; o[k + 3] = a.w;
-  }
-}
-
+// V consecutive channels per thread (chanvec.h ldv / stv / ldp): 8 (one 16-B bf16 access, two 16-B f32 accesses)
+// when C % 8 == 0, else 4.  Per-channel parameters are read as float4s from L1/L2.
 static int vec_for(int C) { return (C % 8 == 0 && ((C / 8) <= kThreads || (C / 8) % kThreads == 0)) ? 8 : 4; }
 
 // Block layout for per-channel reductions: tpr threads cover one row (V channels each), rp rows in
@@ -1451,7 +1396,6 @@ static int grid_for(int64_t n4) {
   if (b > 8192) b = 8192;
   return (int)(b < 1 ? 1 : b);
 }
-static bool dt_ok(int dt) { return dt == SV_F32 || dt == SV_BF16; }
 
 }  // namespace bn
 }  // namespace sv
@@ -1770,7 +1714,6 @@ static bool small_geo(int64_t rows, int32_t C, RedGeo& g, int& P, int& rpp) {
   rpp = (int)((rows + P - 1) / P);
   return (int64_t)P * g.rp <= kSmallThreads;
 }
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int sv_bn_small_ok(int64_t rows, int32_t C) {
   RedGeo g;

@@ -10,6 +10,7 @@
 // instruction and the row statistics are two wave64 butterfly sums.  Per-channel weight gradients
 // are accumulated in registers across the rows a wave visits (grid-stride) and combined per
 // workgroup, giving deterministic [nparts][C] partials that sv_reduce_partials folds.
+#include "chanvec.h"
 #include "common.h"
 
 namespace sv {
@@ -137,31 +138,6 @@ __global__ void __launch_bounds__(kLnThreads) ln_bwd_kernel(const TDY* __restric
 // 192/384/768/1536 all fit; ConvNeXt-tiny / small's C = 96 is 4 lanes x 24 channels (NV = 3, 16 rows per
 // wave; C = 32 and 160 are the NV = 1 and 5 forms of the same quad), its statistics a two-step DPP quad
 // butterfly.  The per-lane-channel kernels above serve the other widths.
-template <typename T>
-__device__ __forceinline__ void ld8v(const T* __restrict__ p, float (&v)[8]) {
-  if constexpr (sizeof(T) == 4) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  } else {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(w[j] << 16);
-      v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  }
-}
-template <typename T>
-__device__ __forceinline__ void st8v(T* __restrict__ p, const float (&v)[8]) {
-  if constexpr (sizeof(T) == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-  } else {
-    *reinterpret_cast<uint4*>(p) =
-        make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-  }
-}
 // the row statistics' butterfly over LPR lanes: from the cross-lane unit for groups of >= 16 lanes (common.h
 // xlane_group_sum, bitwise the shuffle form; -DSV_LN_XLANE=0 keeps ds_bpermute shuffles, A/B builds)
 #ifndef SV_LN_XLANE
@@ -196,7 +172,7 @@ __global__ void __launch_bounds__(kLnThreads) ln_fwd_vec_kernel(const TX* __rest
   float s = 0.f;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    ld8v(x + base + (size_t)(l + LPR * j) * 8, v[j]);
+    ld8(x + base + (size_t)(l + LPR * j) * 8, v[j]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += v[j][e];
   }
@@ -213,11 +189,11 @@ __global__ void __launch_bounds__(kLnThreads) ln_fwd_vec_kernel(const TX* __rest
   for (int j = 0; j < NV; ++j) {
     const int c = (l + LPR * j) * 8;
     float wv[8], bv[8], o[8];
-    ld8v(w + c, wv);
-    ld8v(b + c, bv);
+    ld8(w + c, wv);
+    ld8(b + c, bv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (v[j][e] - mu) * rs * wv[e] + bv[e];
-    st8v(y + base + c, o);
+    st8(y + base + c, o);
   }
   if (l == 0) {
     mean[r] = mu;
@@ -244,7 +220,7 @@ __global__ void __launch_bounds__(kLnThreads) ln_bwd_vec_kernel(const TDY* __res
   float wr[NV][8], adw[NV][8], adb[NV][8];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    ld8v(w + (l + LPR * j) * 8, wr[j]);
+    ld8(w + (l + LPR * j) * 8, wr[j]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) adw[j][e] = adb[j][e] = 0.f;
   }
@@ -255,8 +231,8 @@ __global__ void __launch_bounds__(kLnThreads) ln_bwd_vec_kernel(const TDY* __res
     if (!ok) r = 0;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      ld8v(dy + (size_t)r * C + (l + LPR * j) * 8, nd[j]);
-      ld8v(x + (size_t)r * C + (l + LPR * j) * 8, nx[j]);
+      ld8(dy + (size_t)r * C + (l + LPR * j) * 8, nd[j]);
+      ld8(x + (size_t)r * C + (l + LPR * j) * 8, nx[j]);
       if (!ok) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) nd[j][e] = 0.f;  // contributes nothing to dw/db
@@ -301,11 +277,11 @@ __global__ void __launch_bounds__(kLnThreads) ln_bwd_vec_kernel(const TDY* __res
         for (int e = 0; e < 8; ++e) o[e] = rs * (d[j][e] * wr[j][e] - s1 - xh[j][e] * s2);
         if (accumulate) {
           float old[8];
-          ld8v(p, old);
+          ld8(p, old);
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] += old[e];
         }
-        st8v(p, o);
+        st8(p, o);
       }
     }
   }

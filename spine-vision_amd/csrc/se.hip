@@ -17,14 +17,14 @@
 //     ceil(HW / P) rows; in a part, thread (rsub, channel group) adds rows r0 + rsub, + rp, ... ascending (rp = 256 /
 //     (C / 8) rows in flight), the rp threads of a channel group are added in rsub order, and the consumer adds the P
 //     parts in part order;
-//   * a matvec row (fc1, fc2): lane l multiplies-adds (fmaf) elements 4 l + 256 j + (0..3) ascending into one
-//     accumulator, then the 64 lanes are added by the xor butterfly wave_sum;
-//   * a transposed matvec column (the gate backward): 16 k-groups, group q fmaf-accumulating k = q, q + 16, ...
-//     ascending, then the groups added in q order;
-//   * sums over the batch (weight gradients, BatchNorm sums): b ascending, fmaf.
+//   * the matvec rows (fc1, fc2), the transposed matvec columns (the gate backward) and the outer products over the
+//     batch (the gate's weight gradients): se_core.h;
+//   * the BatchNorm sums over the batch: b ascending, fmaf.
 #include <math.h>
 
+#include "chanvec.h"
 #include "common.h"
+#include "se_core.h"
 
 namespace sv {
 namespace se {
@@ -33,37 +33,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxC = 2048;
 constexpr int kMaxParts = 32;
 
-__device__ __forceinline__ void ldv(const void* p, int dt, size_t i, float (&o)[8]) {
-  if (dt == SV_F32) {
-    const float* f = reinterpret_cast<const float*>(p) + i;
-    const float4 a = *reinterpret_cast<const float4*>(f), b = *reinterpret_cast<const float4*>(f + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-  } else {
-    const uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(p) + i);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      o[2 * k] = __uint_as_float(w[k] << 16);
-      o[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-    }
-  }
-}
-__device__ __forceinline__ void stv(void* p, int dt, size_t i, const float (&v)[8]) {
-  if (dt == SV_F32) {
-    float* f = reinterpret_cast<float*>(p) + i;
-    *reinterpret_cast<float4*>(f) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(f + 4) = make_float4(v[4], v[5], v[6], v[7]);
-  } else {
-    *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p) + i) =
-        make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-  }
-}
-__device__ __forceinline__ void ldp(const float* p, int c, float (&o)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p + c), b = *reinterpret_cast<const float4*>(p + c + 4);
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-
-static bool dt_ok(int dt) { return dt == SV_F32 || dt == SV_BF16; }
 // C a power of two in 16..2048: C / 8 threads cover a row and divide the block
 static bool c_ok(int C) { return C >= 16 && C <= kMaxC && (C & (C - 1)) == 0; }
 
@@ -173,25 +142,9 @@ __global__ void __launch_bounds__(kThreads) fc_kernel(FcArgs a) {
     for (int k = t; k < K; k += kThreads) xs[k] = a.x[(size_t)b * K + k];
   }
   __syncthreads();
-  const int lane = t & 63, w = t >> 6;
-  for (int i = 0; i < kFcRows / 4; ++i) {
-    const int n = blockIdx.x * kFcRows + w * (kFcRows / 4) + i;  // wave-uniform
-    if (n >= a.N) break;
-    const float* wr = a.W + (size_t)n * K;
-    float acc = 0.f;
-    for (int k = lane * 4; k < K; k += 256) {
-      const float4 wv = *reinterpret_cast<const float4*>(wr + k);
-      acc = fmaf(wv.x, xs[k], acc);
-      acc = fmaf(wv.y, xs[k + 1], acc);
-      acc = fmaf(wv.z, xs[k + 2], acc);
-      acc = fmaf(wv.w, xs[k + 3], acc);
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) {
-      const float v = acc + a.bias[n];
-      a.out[(size_t)b * a.N + n] = FC == 1 ? fmaxf(v, 0.f) : 1.0f / (1.0f + expf(-v));
-    }
-  }
+  matvec_rows<kFcRows>(xs, a.W, a.bias, a.N, K, [&](int n, float v) {
+    a.out[(size_t)b * a.N + n] = FC == 1 ? fmaxf(v, 0.f) : 1.0f / (1.0f + expf(-v));
+  });
 }
 
 // ---- join: out = relu(z * gate + shortcut) --------------------------------------------------------------------------
@@ -275,56 +228,10 @@ __global__ void __launch_bounds__(kThreads) tmatvec_kernel(TmArgs a) {
     for (int k = t; k < K; k += kThreads) vs[k] = a.v[(size_t)b * K + k];
   }
   __syncthreads();
-  const int q = t >> 4, col = (t & 15) * 4, n0 = blockIdx.x * 64 + col;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (n0 < N) {
-    for (int k = q; k < K; k += 16) {
-      const float4 wv = *reinterpret_cast<const float4*>(a.W + (size_t)k * N + n0);
-      const float x = vs[k];
-      acc.x = fmaf(x, wv.x, acc.x);
-      acc.y = fmaf(x, wv.y, acc.y);
-      acc.z = fmaf(x, wv.z, acc.z);
-      acc.w = fmaf(x, wv.w, acc.w);
-    }
-  }
-  red[q][col] = acc.x;
-  red[q][col + 1] = acc.y;
-  red[q][col + 2] = acc.z;
-  red[q][col + 3] = acc.w;
-  __syncthreads();
-  const int n = blockIdx.x * 64 + t;
-  if (t < 64 && n < N) {
-    float s = red[0][t];
-    for (int j = 1; j < 16; ++j) s += red[j][t];
+  tmatvec_cols(vs, red, a.W, N, K, [&](int n, float s) {
     if constexpr (TM == 1) s = a.hidden[(size_t)b * N + n] > 0.f ? s : 0.f;
     a.out[(size_t)b * N + n] = s;
-  }
-}
-
-// dW[m][n] += sum_b u[b][m] v[b][n],  db[m] += sum_b u[b][m]   (one thread per 4 columns of one row)
-__global__ void __launch_bounds__(kThreads) outer_kernel(const float* __restrict__ u, const float* __restrict__ v,
-                                                         float* __restrict__ dW, float* __restrict__ db, int B, int M,
-                                                         int N) {
-  const int n4 = N / 4;
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= (int64_t)M * n4) return;
-  const int m = (int)(i / n4), n = (int)(i % n4) * 4;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  float sb = 0.f;
-  for (int b = 0; b < B; ++b) {
-    const float x = u[(size_t)b * M + m];
-    const float4 w = *reinterpret_cast<const float4*>(v + (size_t)b * N + n);
-    acc.x = fmaf(x, w.x, acc.x);
-    acc.y = fmaf(x, w.y, acc.y);
-    acc.z = fmaf(x, w.z, acc.z);
-    acc.w = fmaf(x, w.w, acc.w);
-    sb += x;
-  }
-  float4* o = reinterpret_cast<float4*>(dW + (size_t)m * N + n);
-  float4 d = *o;
-  d.x += acc.x; d.y += acc.y; d.z += acc.z; d.w += acc.w;
-  *o = d;
-  if (n == 0) db[m] += sb;
+  });
 }
 
 // the BatchNorm's sums of dz = g * gate + dpool / HW over (b, hw):  sums[0][c] = sum dz,  sums[1][c] = sum dz xhat
@@ -528,9 +435,9 @@ extern "C" int sv_se_bwd_gate(const float* part, int32_t nparts, const float* ym
   p.v = dh; p.W = w1; p.out = dpool; p.N = C; p.K = rd;
   tmatvec_kernel<2><<<dim3((C + 63) / 64, B), kThreads, 0, s>>>(p);
   if (int rc = check_launch("sv_se_bwd_gate: fc1^T")) return rc;
-  outer_kernel<<<(int)(((int64_t)C * (rd / 4) + kThreads - 1) / kThreads), kThreads, 0, s>>>(dsig, hidden, dw2, db2, B, C, rd);
+  launch_outer(dsig, hidden, dw2, db2, B, C, rd, s);
   if (int rc = check_launch("sv_se_bwd_gate: dw2")) return rc;
-  outer_kernel<<<(int)(((int64_t)rd * (C / 4) + kThreads - 1) / kThreads), kThreads, 0, s>>>(dh, pooled, dw1, db1, B, rd, C);
+  launch_outer(dh, pooled, dw1, db1, B, rd, C, s);
   if (int rc = check_launch("sv_se_bwd_gate: dw1")) return rc;
   bn_sums_kernel<<<(C + kThreads - 1) / kThreads, kThreads, 0, s>>>(sg, sgx, gate, dpool, ymean, mean, rstd, sums, dgamma,
                                                                   dbeta, batch_stats, B, C);

@@ -15,8 +15,8 @@ Calls                                                   -> test here
 Inputs.  Each call is judged alone: its inputs are the f32 (or bf16) roundings of the float64 results of the calls before
 it, not those calls' outputs.  SiLU has no ties, so no element is excluded.
 
-Bounds, derived from the summation orders and rounding points documented at the top of csrc/mbconv.hip and asserted at
-2 x for EVERY element (u = 2^-24):
+Bounds, derived from the summation orders and rounding points documented at the top of csrc/mbconv.hip and
+csrc/se_core.h and asserted at 2 x for EVERY element (u = 2^-24):
     pre              e_pre = u (3 |t| + |pre|), t = gamma rstd (y - mean): gamma rstd, y - mean, the fmaf
     sigmoid          4 u sig (expf within 1 ulp = 2 u, one add, one correctly rounded division), slope <= 1/4 on the argument
     silu             |silu'| <= 1.1 on the argument's bound, plus 5 u |silu| (the sigmoid and the product)
@@ -35,7 +35,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _conv_ref import BF, F32, F64, U8, U24, acc_bound
+from _calls_harness import f32, judge as _judge, mv_depth, store, tm_depth
+from _conv_ref import BF, F32, F64, U24, acc_bound
 from spine_vision_amd import kernels as K
 from spine_vision_amd import native as nv
 
@@ -114,31 +115,7 @@ def twice(where, once):
     return first
 
 
-def judge(where, got, refs):
-    """every element of every output within 2 x bound; prints the largest error / bound per output"""
-    figs = []
-    for n, (ref, bound) in refs.items():
-        g = got[n].double().reshape(ref.shape)
-        err = (g - ref).abs()
-        ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))
-        ratio = torch.where(torch.isfinite(err), ratio, torch.full_like(ratio, float("inf")))
-        worst = float(ratio.max())
-        figs.append(f"{n} err {float(err.max()):.3e} ratio {worst:.3f}")
-        if not worst <= 2.0:
-            flat = int(ratio.reshape(-1).argmax())
-            print(f"[mbconv_calls] {where}: " + ", ".join(figs))
-            pytest.fail(f"{where} {n}: {int((ratio > 2).sum())} of {ratio.numel()} elements beyond 2 x bound; worst at flat "
-                        f"{flat}: got {float(g.reshape(-1)[flat]):.9g}, float64 {float(ref.reshape(-1)[flat]):.9g}, "
-                        f"bound {float(bound.reshape(-1)[flat]):.3e}, error / bound {worst:.3g}")
-    print(f"[mbconv_calls] {where}: " + ", ".join(figs))
-
-
-def store(ref, dtype):
-    return U8 * ref.abs() if dtype == BF else torch.zeros_like(ref)
-
-
-def f32(t):
-    return t.float().double()
+judge = functools.partial(_judge, "mbconv_calls")
 
 
 # -------------------------------------------------------------------------------------------- geometry, restated
@@ -152,14 +129,6 @@ def geo(rows):
 def part_sums(t, P, rpp):
     """[B, rows, C] float64 -> [B, P, C]: sums over runs of rpp rows (the last one short)"""
     return torch.stack([t[:, p * rpp:(p + 1) * rpp].sum(1) for p in range(P)], 1)
-
-
-def mv_depth(Kd):
-    return 4 * (-(-Kd // 256)) + 7
-
-
-def tm_depth(Kd):
-    return -(-Kd // 16) + 15
 
 
 # ---------------------------------------------------------------------------------------- float64 formulas, bounds

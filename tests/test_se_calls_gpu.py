@@ -19,8 +19,8 @@ before it, not those calls' outputs.  The join and the three backward calls run 
 BN'd: the backward's mask is that form's stored output).  ReLU ties need no mask: the backward takes its mask from the ``act`` input, which
 the reference shares.
 
-Bounds, derived from the summation orders and rounding points documented at the top of csrc/se.hip and asserted at 2 x
-for EVERY element (u = 2^-24):
+Bounds, derived from the summation orders and rounding points documented at the top of csrc/se.hip and csrc/se_core.h
+and asserted at 2 x for EVERY element (u = 2^-24):
     per-image sums   depth u sum |t|, depth = ceil(rpp / rp) + (rp - 1) (a thread's serial rows, then the rp row groups);
                      the consumer's fold of P parts adds (P - 1) u sum |part|
     matvec           depth u sum |w x|, depth = 4 ceil(K / 256) + 6 + 1 (the lane's fmaf chain, the 64-lane butterfly,
@@ -38,6 +38,7 @@ import pytest
 import torch
 
 import _conv_ref as CR
+from _calls_harness import f32, judge as _judge, mv_depth, store, tm_depth
 from _conv_ref import BF, F32, F64, U8, U24
 from spine_vision_amd import kernels as K
 from spine_vision_amd import native as nv
@@ -106,27 +107,7 @@ def twice(where, once):
     return first
 
 
-def judge(where, got, refs):
-    """every element of every output within 2 x bound; prints the largest error / bound per output"""
-    figs = []
-    for n, (ref, bound) in refs.items():
-        g = got[n].double().reshape(ref.shape)
-        err = (g - ref).abs()
-        ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))
-        ratio = torch.where(torch.isfinite(err), ratio, torch.full_like(ratio, float("inf")))
-        worst = float(ratio.max())
-        figs.append(f"{n} err {float(err.max()):.3e} ratio {worst:.3f}")
-        if not worst <= 2.0:
-            flat = int(ratio.reshape(-1).argmax())
-            print(f"[se_calls] {where}: " + ", ".join(figs))
-            pytest.fail(f"{where} {n}: {int((ratio > 2).sum())} of {ratio.numel()} elements beyond 2 x bound; worst at flat "
-                        f"{flat}: got {float(g.reshape(-1)[flat]):.9g}, float64 {float(ref.reshape(-1)[flat]):.9g}, "
-                        f"bound {float(bound.reshape(-1)[flat]):.3e}, error / bound {worst:.3g}")
-    print(f"[se_calls] {where}: " + ", ".join(figs))
-
-
-def store(ref, dtype):
-    return U8 * ref.abs() if dtype == BF else torch.zeros_like(ref)
+judge = functools.partial(_judge, "se_calls")
 
 
 # -------------------------------------------------------------------------------------------- geometry, restated
@@ -141,18 +122,6 @@ def geo(HW, C):
 def part_sums(t, P, rpp):
     """[B, HW, C] float64 -> [B, P, C]: sums over runs of rpp rows (the last one short)"""
     return torch.stack([t[:, p * rpp:(p + 1) * rpp].sum(1) for p in range(P)], 1)
-
-
-def mv_depth(Kd):
-    return 4 * (-(-Kd // 256)) + 7
-
-
-def tm_depth(Kd):
-    return -(-Kd // 16) + 15
-
-
-def f32(t):
-    return t.float().double()
 
 
 # ------------------------------------------------------------------------------------------------------ operands
