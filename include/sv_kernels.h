@@ -993,6 +993,23 @@ int sv_mbse_bwd_apply(const void* da, int32_t da_dtype, const void* y, int32_t y
                       const float* rstd, const float* gamma, const float* beta, const float* gate, const float* dpool,
                       void* dpre, int32_t dpre_dtype, float* part, int32_t B, int32_t HW, int32_t C, sv_stream_t stream);
 
+/* ---- depthwise 5x5 (csrc/dwconv5.hip, ABI v11): the k = 5 InvertedResidual blocks of EfficientNet-B0..B4 ----------
+ * The sv_dwconv3_* signatures with pad 2: NHWC f32 or bf16 tensors, f32 arithmetic rounded once at the store,
+ * w = the torch weight [C][1][5][5] f32, stride 1 | 2, OH = (H - 1) / stride + 1, any H, W >= 1, C a multiple of 32 up
+ * to 3840; other shapes return SV_ERR_UNSUPPORTED before any launch.  All pointers 16-B aligned.  No atomics: one fmaf
+ * chain per output element over (ky, kx) ascending; the weight gradient's order is stated in csrc/dwconv5.hip.
+ *   sv_dwconv5_bwd_weight  part [sv_dwconv5_bwd_weight_nparts][25][C], folded in part order into dw [C][1][5][5]
+ *                          (accumulate: dw +=)
+ * Replaces: the depthwise Conv2d(k = 5) of timm's efficientnet_b* InvertedResidual + autograd.                        */
+int sv_dwconv5_fwd(const void* x, int32_t x_dtype, const float* w, void* y, int32_t y_dtype, int32_t B, int32_t H,
+                   int32_t W, int32_t C, int32_t stride, sv_stream_t stream);
+int sv_dwconv5_bwd_data(const void* dy, int32_t dy_dtype, const float* w, void* dx, int32_t dx_dtype, int32_t B,
+                        int32_t H, int32_t W, int32_t C, int32_t stride, sv_stream_t stream);
+int sv_dwconv5_bwd_weight_nparts(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride);
+int sv_dwconv5_bwd_weight(const void* dy, int32_t dy_dtype, const void* x, int32_t x_dtype, float* part, float* dw,
+                          int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                          sv_stream_t stream);
+
 /* ---- classification loss (csrc/loss.hip, ABI v7) ------------------------------------------------
  * The multi-task loss over the fused head's logits [B][K] (f32, row-major) in one launch: loss[0] =
  * sum_k weight_k * loss_k, and dlogits [B][K] = d(loss[0]) / d(logits) (every column of a task's range

@@ -1,6 +1,9 @@
 """EfficientNetV2-S / M / L backbone on the gfx950 kernel library -- drop-in for
 ``timm.create_model("efficientnetv2_{s,m,l}", num_classes=0)`` (timm ``efficientnet.py`` ``_gen_efficientnetv2_*``, the
-non-``tf_``, non-``rw`` variants: symmetric padding k // 2, BatchNorm eps 1e-5, SiLU, drop-path 0).
+non-``tf_``, non-``rw`` variants: symmetric padding k // 2, BatchNorm eps 1e-5, SiLU, drop-path 0) -- and, on the same
+block routines, EfficientNet-B0 .. B4 (``EfficientNetHip`` at the end of the file: ``efficientnet_b{0..4}``, the
+``DepthwiseSeparable`` first stage, 5x5 depthwise convolutions on csrc/dwconv5.hip, every stored channel stride a
+multiple of 32 and every squeeze-and-excitation hidden width a multiple of 4, zero-padded as described below).
 
 * Same module tree / ``state_dict`` keys as timm: ``conv_stem``, ``bn1``, ``blocks.{stage}.{i}.*``, ``conv_head``,
   ``bn2``; ConvBnAct (``conv``, ``bn1``), EdgeResidual (``conv_exp``, ``bn1``, ``conv_pwl``, ``bn2``) and InvertedResidual
@@ -22,6 +25,7 @@ non-``tf_``, non-``rw`` variants: symmetric padding k // 2, BatchNorm eps 1e-5, 
 
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Callable
@@ -48,6 +52,33 @@ EFFNETV2_CFGS = {
 }
 HEAD_WIDTH = 1280
 BN_EPS = 1e-5
+
+
+def _round_channels(v: float) -> int:
+    """timm round_channels(v, 8, round_limit=0.9)"""
+    n = max(8, int(v + 4) // 8 * 8)
+    return n + 8 if n < 0.9 * v else n
+
+
+# EfficientNet-B0's stages: (type, repeats, kernel, stride of the first block, expansion, out channels), type ``ds``
+# (DepthwiseSeparable) or ``ir``; B1..B4 scale the widths by w (round_channels) and the repeats by d (ceil)
+_B0_STAGES = (("ds", 1, 3, 1, 1, 16), ("ir", 2, 3, 2, 6, 24), ("ir", 2, 5, 2, 6, 40), ("ir", 3, 3, 2, 6, 80),
+              ("ir", 3, 5, 1, 6, 112), ("ir", 4, 5, 2, 6, 192), ("ir", 1, 3, 1, 6, 320))
+
+
+def _scaled(w: float, d: float) -> tuple:
+    stages = tuple((t, math.ceil(r * d), k, s, e, _round_channels(c * w)) for t, r, k, s, e, c in _B0_STAGES)
+    return _round_channels(32 * w), stages, _round_channels(HEAD_WIDTH * w)
+
+
+# name -> (stem width, stages, num_features)
+EFFNET_CFGS = {f"efficientnet_b{i}": _scaled(w, d)
+               for i, (w, d) in enumerate(((1.0, 1.0), (1.0, 1.1), (1.1, 1.2), (1.2, 1.4), (1.4, 1.8)))}
+
+
+def _r32(c: int) -> int:
+    """the stored channel stride of an EfficientNet-B activation: the streaming kernels take multiples of 32"""
+    return -(-c // 32) * 32
 
 
 def _pow2(c: int) -> int:
@@ -94,18 +125,39 @@ class SqueezeExcite(nn.Module):
 class InvertedResidual(nn.Module):
     kind = "ir"
 
-    def __init__(self, cin: int, cout: int, stride: int, expand: int) -> None:
+    def __init__(self, cin: int, cout: int, stride: int, expand: int, k: int = 3) -> None:
         super().__init__()
         mid = cin * expand
         self.conv_pw = nn.Conv2d(cin, mid, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(mid, eps=BN_EPS)
-        self.conv_dw = nn.Conv2d(mid, mid, 3, stride=stride, padding=1, groups=mid, bias=False)
+        self.conv_dw = nn.Conv2d(mid, mid, k, stride=stride, padding=k // 2, groups=mid, bias=False)
         self.bn2 = nn.BatchNorm2d(mid, eps=BN_EPS)
         # timm: se_ratio 0.25 of the block's INPUT channels (se_from_exp=False), not of the expanded width
         self.se = SqueezeExcite(mid, cin // 4)
         self.conv_pwl = nn.Conv2d(mid, cout, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(cout, eps=BN_EPS)
         self.stride, self.has_skip = stride, stride == 1 and cin == cout
+
+
+class DepthwiseSeparable(nn.Module):
+    """EfficientNet-B's first stage: the InvertedResidual without its expansion (depthwise 3x3 on the block input)"""
+    kind = "ds"
+
+    def __init__(self, cin: int, cout: int, stride: int, k: int = 3) -> None:
+        super().__init__()
+        self.conv_dw = nn.Conv2d(cin, cin, k, stride=stride, padding=k // 2, groups=cin, bias=False)
+        self.bn1 = nn.BatchNorm2d(cin, eps=BN_EPS)
+        self.se = SqueezeExcite(cin, cin // 4)
+        self.conv_pw = nn.Conv2d(cin, cout, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout, eps=BN_EPS)
+        self.stride, self.has_skip = stride, stride == 1 and cin == cout
+
+
+def _mb_parts(blk) -> tuple:
+    """(expand conv, its BatchNorm, the depthwise BatchNorm, project conv, its BatchNorm) of an ir | ds block"""
+    if blk.kind == "ir":
+        return blk.conv_pw, blk.bn1, blk.bn2, blk.conv_pwl, blk.bn3
+    return None, None, blk.bn1, blk.conv_pw, blk.bn2
 
 
 class _EffNetFn(torch.autograd.Function):
@@ -176,9 +228,13 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
                 cin = cout
             stage_mods.append(nn.Sequential(*blocks))
         self.blocks = nn.Sequential(*stage_mods)
-        self.conv_head = nn.Conv2d(cin, HEAD_WIDTH, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(HEAD_WIDTH, eps=BN_EPS)
-        self.num_features = HEAD_WIDTH
+        self._finish_init(cin, HEAD_WIDTH)
+
+    def _finish_init(self, cin: int, num_features: int) -> None:
+        """the head and the run-time state, after ``conv_stem``, ``bn1`` and ``blocks``"""
+        self.conv_head = nn.Conv2d(cin, num_features, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(num_features, eps=BN_EPS)
+        self.num_features = num_features
         self.grad_ready_hook: Callable[[list], None] | None = None
         self._shadow: dict[int, torch.Tensor] | None = None
         self.overlap_wgrad = os.environ.get("SV_SIDE_STREAM", "1") != "0"
@@ -238,6 +294,14 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
         cout = (blk.conv if blk.kind == "cn" else blk.conv_pwl).out_channels
         return self._cs(cout, blk.kind != "ir")
 
+    def _mid_cs(self, c: int) -> int:
+        """stored stride of an InvertedResidual's expanded tensors (the constructor admits multiples of 32 only)"""
+        return c
+
+    def _rd_cs(self, rd: int) -> int:
+        """stored width of a squeeze-and-excitation's hidden vector (the constructor admits multiples of 4 only)"""
+        return rd
+
     # -- operands ----------------------------------------------------------------------------------
     def _zeros(self, key, shape: tuple, dtype, device, fill_rows=None) -> torch.Tensor:
         buf = self._pads.get(key)
@@ -277,6 +341,60 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
         buf = self._zeros(("dense", id(w)), (Cout_s, Cin_s, 3, 3), torch.float32, w.device)
         buf[:Cout, :Cin].copy_(w.detach())
         return buf
+
+    def _dw_w(self, conv: nn.Conv2d, Cs: int) -> torch.Tensor:
+        """A depthwise weight over the stored channels, f32 [Cs][1][k][k] (padded rows zero)."""
+        w = conv.weight
+        C = w.shape[0]
+        if Cs == C:
+            return w.detach()
+        buf = self._zeros(("dw", id(w)), (Cs, *w.shape[1:]), torch.float32, w.device)
+        buf[:C].copy_(w.detach())
+        return buf
+
+    def _se_w(self, se: SqueezeExcite, Cs: int, rds: int) -> tuple:
+        """(w1 [rds][Cs], b1 [rds], w2 [Cs][rds], b2 [Cs]) of a squeeze-and-excitation over the stored widths: the
+        parameters, or zero-padded copies (a padded hidden unit is silu(0) = 0; a padded channel's gate scales a zero)."""
+        ps = se.params()
+        rd, C = ps[0].shape[:2]
+        if (rds, Cs) == (rd, C):
+            return tuple(ps)
+        out = []
+        for i, (p, shape) in enumerate(zip(ps, ((rds, Cs, 1, 1), (rds,), (Cs, rds, 1, 1), (Cs,)))):
+            buf = self._zeros(("se", id(p)), shape, torch.float32, p.device)
+            buf[tuple(slice(0, n) for n in p.shape)].copy_(p.detach())
+            out.append(buf)
+        return tuple(out)
+
+    def _se_grads(self, se: SqueezeExcite, Cs: int, rds: int) -> tuple:
+        """(dw1, db1, dw2, db2) accumulators over the stored widths, and the fold into p.grad for a padded one (the
+        gradients of padded rows / columns are dropped)."""
+        ps = se.params()
+        rd, C = ps[0].shape[:2]
+        if (rds, Cs) == (rd, C):
+            return (*map(self._grad, ps), lambda: None)
+        scr = [torch.zeros(shape, device=ps[0].device, dtype=torch.float32)
+               for shape in ((rds, Cs, 1, 1), (rds,), (Cs, rds, 1, 1), (Cs,))]
+
+        def fold():
+            for p, t in zip(ps, scr):
+                self._grad(p).add_(t[tuple(slice(0, n) for n in p.shape)])
+        return (*scr, fold)
+
+    def _dw_wgrad(self, conv: nn.Conv2d, dy4d, x4d):
+        """weight-gradient job of a depthwise convolution: into p.grad, or -- padded channels -- through a scratch"""
+        g = self._grad(conv.weight)
+        C, k, st = conv.weight.shape[0], conv.kernel_size[0], conv.stride[0]
+        wgrad = K.dwconv5_bwd_weight if k == 5 else K.dwconv3_bwd_weight
+
+        def job(pol):
+            if dy4d.shape[-1] == C:
+                wgrad(dy4d, x4d, st, dw=g, accumulate=True)
+            else:
+                tmp = torch.empty(dy4d.shape[-1], 1, k, k, device=g.device, dtype=torch.float32)
+                wgrad(dy4d, x4d, st, dw=tmp, accumulate=False)
+                g.add_(tmp[:C])
+        return job
 
     def _bn_ref(self, bn: nn.BatchNorm2d, Cs: int) -> _Bn:
         C = bn.num_features
@@ -346,7 +464,7 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
     # -- forward -----------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda:
-            raise RuntimeError("EfficientNetV2Hip runs on the MI355X kernel library only (got a CPU tensor)")
+            raise RuntimeError(f"{type(self).__name__} runs on the MI355X kernel library only (got a CPU tensor)")
         x = x.contiguous() if x.dtype == torch.uint8 else x.float().contiguous()
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if need_grad:
@@ -379,10 +497,11 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
             x = out
         # head: conv 1x1 -> BatchNorm + SiLU -> global average pool
         B, H, W, Cs = x.shape
-        wh = self._lin_w(self.conv_head, HEAD_WIDTH, Cs, cache)
+        nf = self.num_features
+        wh = self._lin_w(self.conv_head, nf, Cs, cache)
         yh, part = self._lin(x.view(-1, Cs), wh)
-        bh = self._stats(self._bn_ref(self.bn2, HEAD_WIDTH), yh, part)
-        a = K.bn_silu_fwd(yh, bh.ref, out_dtype=act).view(B, H, W, HEAD_WIDTH)
+        bh = self._stats(self._bn_ref(self.bn2, nf), yh, part)
+        a = K.bn_silu_fwd(yh, bh.ref, out_dtype=act).view(B, H, W, nf)
         feat = K.avgpool_fwd(a)
         if save:
             tape.head = (x, yh, bh, wh)
@@ -410,23 +529,27 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
             b2 = self._stats(self._bn_ref(blk.bn2, out_s), y2, part2)
             out = K.bn_act(y2, b2.mean, b2.rstd, b2.gamma, b2.beta, res=res, relu=False, out_dtype=act)
             return out.view(B, y1.shape[1], y1.shape[2], out_s), (y1, b1, wp, s, a1, y2, b2, w2)
-        mid = blk.conv_pw.out_channels
-        w1 = self._lin_w(blk.conv_pw, mid, Cs, cache)
-        y1, part1 = self._lin(x.view(-1, Cs), w1)
-        b1 = self._stats(self._bn_ref(blk.bn1, mid), y1, part1)
-        a1 = K.bn_silu_fwd(y1, b1.ref, out_dtype=act).view(B, H, W, mid)
-        wdw = blk.conv_dw.weight.detach()
-        y2 = K.dwconv3_fwd(a1, wdw, blk.stride, out_dtype=act)
+        # ir | ds: (1x1 expand -> BatchNorm + SiLU ->) depthwise -> BatchNorm + SiLU -> SE -> 1x1 project -> BatchNorm
+        conv_e, bn_e, bn_d, conv_p, bn_p = _mb_parts(blk)
+        if conv_e is None:
+            mid, y1, b1, w1, a1 = Cs, None, None, None, x
+        else:
+            mid = self._mid_cs(conv_e.out_channels)
+            w1 = self._lin_w(conv_e, mid, Cs, cache)
+            y1, part1 = self._lin(x.view(-1, Cs), w1)
+            b1 = self._stats(self._bn_ref(bn_e, mid), y1, part1)
+            a1 = K.bn_silu_fwd(y1, b1.ref, out_dtype=act).view(B, H, W, mid)
+        dw_fwd = K.dwconv5_fwd if blk.conv_dw.kernel_size[0] == 5 else K.dwconv3_fwd
+        y2 = dw_fwd(a1, self._dw_w(blk.conv_dw, mid), blk.stride, out_dtype=act)
         _, OH, OW, _ = y2.shape
-        b2 = self._stats(self._bn_ref(blk.bn2, mid), y2.view(-1, mid))
-        # s = silu(bn2(y2)) is never stored: the squeeze, the scale and both backward passes recompute it from y2
-        se = blk.se
-        state = K.mbse_excite(K.mbse_squeeze(y2, b2.ref), OH * OW, se.conv_reduce.weight, se.conv_reduce.bias,
-                              se.conv_expand.weight, se.conv_expand.bias)
+        b2 = self._stats(self._bn_ref(bn_d, mid), y2.view(-1, mid))
+        # s = silu(bn(y2)) is never stored: the squeeze, the scale and both backward passes recompute it from y2
+        sew = self._se_w(blk.se, mid, self._rd_cs(blk.se.conv_reduce.out_channels))
+        state = K.mbse_excite(K.mbse_squeeze(y2, b2.ref), OH * OW, *sew)
         a2 = K.mbse_scale(y2, b2.ref, state[3], out_dtype=act)
-        w3 = self._lin_w(blk.conv_pwl, out_s, mid, cache)
+        w3 = self._lin_w(conv_p, out_s, mid, cache)
         y3, part3 = self._lin(a2.view(-1, mid), w3)
-        b3 = self._stats(self._bn_ref(blk.bn3, out_s), y3, part3)
+        b3 = self._stats(self._bn_ref(bn_p, out_s), y3, part3)
         out = K.bn_act(y3, b3.mean, b3.rstd, b3.gamma, b3.beta, res=res, relu=False, out_dtype=act)
         return out.view(B, OH, OW, out_s), (y1, b1, w1, a1, y2, b2, state, a2, y3, b3, w3)
 
@@ -527,34 +650,41 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
             params = [blk.conv_pwl.weight, blk.bn2.weight, blk.bn2.bias, blk.conv_exp.weight, blk.bn1.weight, blk.bn1.bias]
         else:
             y1, b1, w1, a1, y2, b2, state, a2, y3, b3, w3 = saved
-            g = self._grad
+            conv_e, bn_e, bn_d, conv_p, bn_p = _mb_parts(blk)
             se = blk.se
             Cm, Co = y2.shape[-1], y3.shape[-1]
-            _, OH, OW, _ = y2.shape
+            rds = self._rd_cs(se.conv_reduce.out_channels)
             dg, db, fold = self._bn_grads(b3)
             dy3 = K.bn_bwd(d.view(-1, Co), y3, b3.mean, b3.rstd, b3.gamma, dgamma=dg, dbeta=db, dx_dtype=act,
                            batch_stats=batch_stats)
             fold()
-            jobs.append(self._lin_wgrad(blk.conv_pwl, dy3, a2.view(-1, Cm)))
+            jobs.append(self._lin_wgrad(conv_p, dy3, a2.view(-1, Cm)))
             da2 = self._lin_dgrad(dy3, w3, act).view(y2.shape)
-            # pass A: per-image sum_hw da s; the gate's backward; pass B: dpre and bn2's backward partials
+            # pass A: per-image sum_hw da s; the gate's backward; pass B: dpre and the depthwise BatchNorm's partials
             part = K.mbse_bwd_stats(da2, y2, b2.ref)
-            dpool = K.mbse_bwd_gate(part, state, se.conv_reduce.weight, se.conv_expand.weight,
-                                    dw1=g(se.conv_reduce.weight), db1=g(se.conv_reduce.bias),
-                                    dw2=g(se.conv_expand.weight), db2=g(se.conv_expand.bias))
+            sew = self._se_w(se, Cm, rds)
+            dw1, db1, dw2, db2, fold = self._se_grads(se, Cm, rds)
+            dpool = K.mbse_bwd_gate(part, state, sew[0], sew[2], dw1=dw1, db1=db1, dw2=dw2, db2=db2)
+            fold()
             dpre, bpart = K.mbse_bwd_apply(da2, y2, b2.ref, state[3], dpool, out_dtype=act)
+            dg, db, fold = self._bn_grads(b2)
             dy2 = K.bn_bwd_from_partials(dpre.view(-1, Cm), y2.view(-1, Cm), b2.mean, b2.rstd, b2.gamma, bpart,
-                                         dgamma=g(blk.bn2.weight), dbeta=g(blk.bn2.bias), dx_dtype=act,
-                                         batch_stats=batch_stats).view(y2.shape)
-            wdw, gdw, st = blk.conv_dw.weight.detach(), g(blk.conv_dw.weight), blk.stride
-            jobs.append(lambda pol: K.dwconv3_bwd_weight(dy2, a1, st, dw=gdw, accumulate=True))
-            da1 = K.dwconv3_bwd_data(dy2, wdw, H, W, st, dx_dtype=act)
-            dy1 = K.bn_silu_bwd(da1.view(-1, Cm), y1, b1.ref, dgamma=g(blk.bn1.weight), dbeta=g(blk.bn1.bias),
-                                dx_dtype=act, batch_stats=batch_stats)
-            jobs.append(self._lin_wgrad(blk.conv_pw, dy1, x_in.view(-1, Cs)))
-            dx = self._lin_dgrad(dy1, w1, self.grad_dtype).view(x_in.shape)
-            params = [blk.conv_pwl.weight, blk.bn3.weight, blk.bn3.bias, *se.params(), blk.bn2.weight, blk.bn2.bias,
-                      blk.conv_dw.weight, blk.bn1.weight, blk.bn1.bias, blk.conv_pw.weight]
+                                         dgamma=dg, dbeta=db, dx_dtype=act, batch_stats=batch_stats).view(y2.shape)
+            fold()
+            jobs.append(self._dw_wgrad(blk.conv_dw, dy2, a1))
+            dw_bwd = K.dwconv5_bwd_data if blk.conv_dw.kernel_size[0] == 5 else K.dwconv3_bwd_data
+            da1 = dw_bwd(dy2, self._dw_w(blk.conv_dw, Cm), H, W, blk.stride, dx_dtype=act)
+            params = [conv_p.weight, bn_p.weight, bn_p.bias, *se.params(), bn_d.weight, bn_d.bias, blk.conv_dw.weight]
+            if conv_e is None:
+                dx = da1
+            else:
+                dg, db, fold = self._bn_grads(b1)
+                dy1 = K.bn_silu_bwd(da1.view(-1, Cm), y1, b1.ref, dgamma=dg, dbeta=db, dx_dtype=act,
+                                    batch_stats=batch_stats)
+                fold()
+                jobs.append(self._lin_wgrad(conv_e, dy1, x_in.view(-1, Cs)))
+                dx = self._lin_dgrad(dy1, w1, self.grad_dtype).view(x_in.shape)
+                params += [bn_e.weight, bn_e.bias, conv_e.weight]
         if blk.has_skip:
             K.mb_add(dx, d)
         self._flush(jobs, params, side, keep, deferred)
@@ -571,7 +701,7 @@ class EfficientNetV2Hip(ExplicitBackward, nn.Module):
         # head
         x, yh, bh, wh = tape.head
         d = K.avgpool_bwd(dfeat, tape.out_shape, dx_dtype=self.grad_dtype)
-        dy = K.bn_silu_bwd(d.view(-1, HEAD_WIDTH), yh, bh.ref, dgamma=self._grad(self.bn2.weight),
+        dy = K.bn_silu_bwd(d.view(-1, self.num_features), yh, bh.ref, dgamma=self._grad(self.bn2.weight),
                            dbeta=self._grad(self.bn2.bias), dx_dtype=act, batch_stats=bs)
         d = self._lin_dgrad(dy, wh, self.grad_dtype).view(x.shape)
         self._flush([self._lin_wgrad(self.conv_head, dy, x.view(-1, x.shape[-1]))],
@@ -599,3 +729,66 @@ def create_efficientnetv2(name: str, precision: str = "bf16") -> EfficientNetV2H
         raise ValueError(f"unsupported EfficientNetV2 variant {name!r}")
     stem, stages = EFFNETV2_CFGS[key]
     return EfficientNetV2Hip(stem, stages, precision=precision)
+
+
+class EfficientNetHip(EfficientNetV2Hip):
+    """EfficientNet-B0..B4 -- drop-in for ``timm.create_model("efficientnet_b{0..4}", num_classes=0)`` (the non-``tf_``
+    variants) on the block routines of EfficientNetV2Hip, with what the B series adds: the ``ds`` block, 5x5 depthwise
+    convolutions (csrc/dwconv5.hip), and widths the streaming kernels refuse (16, 24, 40, 88, 144, 240, ...; SE widths
+    6, 10, 22, ...).  Every stored activation has its channel stride rounded up to a multiple of 32 (a power of two where
+    the dense 3x3 stem writes it) and every SE hidden vector to a multiple of 4, with the zero-padding rules of the
+    module docstring: padded channels are exactly zero in every forward tensor and every gradient."""
+
+    def __init__(self, stem: int = 32, stages=EFFNET_CFGS["efficientnet_b0"][1], num_features: int = HEAD_WIDTH,
+                 precision: str = "bf16") -> None:
+        """``stages``: (type, repeats, kernel, stride of the first block, expansion, out channels) per stage, type ``ds``
+        (DepthwiseSeparable) or ``ir`` (InvertedResidual), kernel 3 | 5."""
+        nn.Module.__init__(self)
+        if precision not in ("bf16", "fp32"):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        self.precision = precision
+        self.conv_stem = nn.Conv2d(3, stem, 3, stride=2, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(stem, eps=BN_EPS)
+        cin, stage_mods = stem, []
+        for kind, repeats, k, stride, expand, cout in stages:
+            if kind not in ("ds", "ir") or k not in (3, 5):
+                raise ValueError(f"unknown block type / kernel {kind!r} / {k}")
+            if cin % 8 or cout % 8 or _r32(cin * expand) > K.MB_MAX_C:
+                raise ValueError(f"{kind} {cin} -> {cout} (x{expand}): widths must be multiples of 8 and the depthwise "
+                                 f"width at most {K.MB_MAX_C}")
+            blocks = []
+            for i in range(repeats):
+                s = stride if i == 0 else 1
+                blocks.append(DepthwiseSeparable(cin, cout, s, k) if kind == "ds" else
+                              InvertedResidual(cin, cout, s, expand, k))
+                cin = cout
+            stage_mods.append(nn.Sequential(*blocks))
+        self.blocks = nn.Sequential(*stage_mods)
+        self._finish_init(cin, num_features)
+
+    def _out_cs(self, blk) -> int:
+        return _r32((blk.conv_pw if blk.kind == "ds" else blk.conv_pwl).out_channels)
+
+    def _mid_cs(self, c: int) -> int:
+        return _r32(c)
+
+    def _rd_cs(self, rd: int) -> int:
+        return -(-rd // 4) * 4
+
+    def stored_strides(self) -> list:
+        """(stem output, then per block (input, expanded, output)) stored channel strides"""
+        cs = _pow2(self.conv_stem.out_channels)
+        out = [cs]
+        for blk in self.block_list():
+            mid = cs if blk.kind == "ds" else self._mid_cs(blk.conv_dw.out_channels)
+            out.append((cs, mid, self._out_cs(blk)))
+            cs = self._out_cs(blk)
+        return out
+
+
+def create_efficientnet(name: str, precision: str = "bf16") -> EfficientNetHip:
+    key = name.split(".")[0]
+    if key not in EFFNET_CFGS:
+        raise ValueError(f"unsupported EfficientNet variant {name!r}")
+    stem, stages, num_features = EFFNET_CFGS[key]
+    return EfficientNetHip(stem, stages, num_features, precision=precision)

@@ -2604,7 +2604,8 @@ def avgpool2x2_bwd(dout4d: torch.Tensor, H: int, W: int, dx_dtype=torch.float32,
 
 
 # ----------------------------------------------------------------------------------------------
-# MBConv (csrc/mbconv.hip): depthwise 3x3, BatchNorm + SiLU and the gating squeeze-and-excitation of EfficientNetV2
+# MBConv (csrc/mbconv.hip, csrc/dwconv5.hip): depthwise 3x3 | 5x5, BatchNorm + SiLU and the gating squeeze-and-excitation
+# of EfficientNetV2 and EfficientNet-B0..B4
 # SV_MBCONV=torch: the same wrappers computed with torch ops on the device, f32 arithmetic and the same rounding points
 # (A/B baseline and debugging aid, never the default)
 MBCONV_TORCH = os.environ.get("SV_MBCONV", "") == "torch"
@@ -2719,58 +2720,89 @@ def mb_add(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
     return dst
 
 
-def _dw3_check(who: str, x4d, w, stride: int) -> tuple:
+def _dw_check(who: str, x4d, w, stride: int, k: int) -> tuple:
     B, H, W, C = x4d.shape
     _mb_rows(who, C, x4d)
-    _check(stride in (1, 2) and tuple(w.shape) == (C, 1, 3, 3) and w.dtype == torch.float32 and w.is_contiguous()
-           and w.data_ptr() % 16 == 0, f"{who}: stride 1 | 2 and a contiguous f32 weight [C,1,3,3]")
+    _check(stride in (1, 2) and tuple(w.shape) == (C, 1, k, k) and w.dtype == torch.float32 and w.is_contiguous()
+           and w.data_ptr() % 16 == 0, f"{who}: stride 1 | 2 and a contiguous f32 weight [C,1,{k},{k}]")
     return B, H, W, C
+
+
+def _dwconv_fwd(k: int, x4d, w, stride: int, out_dtype, out) -> torch.Tensor:
+    who = f"dwconv{k}_fwd"
+    B, H, W, C = _dw_check(who, x4d, w, stride, k)
+    out_dtype = out_dtype or x4d.dtype
+    if MBCONV_TORCH:
+        y = torch.nn.functional.conv2d(x4d.float().permute(0, 3, 1, 2), w, stride=stride, padding=k // 2, groups=C)
+        return y.permute(0, 2, 3, 1).contiguous().to(out_dtype)
+    y = _se_out(out, (B, (H - 1) // stride + 1, (W - 1) // stride + 1, C), out_dtype, x4d.device, f"{who}: out")
+    call(f"sv_{who}", ptr(x4d), dt(x4d), ptr(w), ptr(y), dt(y), B, H, W, C, stride)
+    return y
+
+
+def _dwconv_bwd_data(k: int, dy4d, w, H: int, W: int, stride: int, dx_dtype, out) -> torch.Tensor:
+    who = f"dwconv{k}_bwd_data"
+    B, OH, OW, C = _dw_check(who, dy4d, w, stride, k)
+    _check((OH, OW) == ((H - 1) // stride + 1, (W - 1) // stride + 1), f"{who}: shape mismatch")
+    dx_dtype = dx_dtype or dy4d.dtype
+    if MBCONV_TORCH:
+        dx = torch.nn.grad.conv2d_input((B, C, H, W), w, dy4d.float().permute(0, 3, 1, 2), stride=stride,
+                                        padding=k // 2, groups=C)
+        return dx.permute(0, 2, 3, 1).contiguous().to(dx_dtype)
+    dx = _se_out(out, (B, H, W, C), dx_dtype, dy4d.device, f"{who}: out")
+    call(f"sv_{who}", ptr(dy4d), dt(dy4d), ptr(w), ptr(dx), dt(dx), B, H, W, C, stride)
+    return dx
+
+
+def _dwconv_bwd_weight(k: int, dy4d, x4d, stride: int, dw, accumulate: bool) -> torch.Tensor:
+    who = f"dwconv{k}_bwd_weight"
+    B, H, W, C = x4d.shape
+    _mb_rows(who, C, x4d)
+    _mb_rows(who, C, dy4d)
+    _check(stride in (1, 2) and tuple(dy4d.shape) == (B, (H - 1) // stride + 1, (W - 1) // stride + 1, C)
+           and tuple(dw.shape) == (C, 1, k, k) and dw.dtype == torch.float32 and dw.is_contiguous(),
+           f"{who}: dy [B,OH,OW,C], dw f32 [C,1,{k},{k}]")
+    if MBCONV_TORCH:
+        g = torch.nn.grad.conv2d_weight(x4d.float().permute(0, 3, 1, 2), (C, 1, k, k), dy4d.float().permute(0, 3, 1, 2),
+                                        stride=stride, padding=k // 2, groups=C)
+        return dw.add_(g) if accumulate else dw.copy_(g)
+    P = value(f"sv_{who}_nparts", B, H, W, C, stride)
+    part = torch.empty(P, k * k, C, device=x4d.device, dtype=torch.float32)
+    call(f"sv_{who}", ptr(dy4d), dt(dy4d), ptr(x4d), dt(x4d), ptr(part), ptr(dw), int(accumulate), B, H, W, C, stride)
+    return dw
 
 
 def dwconv3_fwd(x4d: torch.Tensor, w: torch.Tensor, stride: int, *, out_dtype=None, out=None) -> torch.Tensor:
     """Depthwise 3x3, pad 1 -> [B, (H-1)//stride+1, (W-1)//stride+1, C]."""
-    B, H, W, C = _dw3_check("dwconv3_fwd", x4d, w, stride)
-    out_dtype = out_dtype or x4d.dtype
-    if MBCONV_TORCH:
-        y = torch.nn.functional.conv2d(x4d.float().permute(0, 3, 1, 2), w, stride=stride, padding=1, groups=C)
-        return y.permute(0, 2, 3, 1).contiguous().to(out_dtype)
-    y = _se_out(out, (B, (H - 1) // stride + 1, (W - 1) // stride + 1, C), out_dtype, x4d.device, "dwconv3_fwd: out")
-    call("sv_dwconv3_fwd", ptr(x4d), dt(x4d), ptr(w), ptr(y), dt(y), B, H, W, C, stride)
-    return y
+    return _dwconv_fwd(3, x4d, w, stride, out_dtype, out)
 
 
 def dwconv3_bwd_data(dy4d: torch.Tensor, w: torch.Tensor, H: int, W: int, stride: int, *, dx_dtype=None,
                      out=None) -> torch.Tensor:
-    B, OH, OW, C = _dw3_check("dwconv3_bwd_data", dy4d, w, stride)
-    _check((OH, OW) == ((H - 1) // stride + 1, (W - 1) // stride + 1), "dwconv3_bwd_data: shape mismatch")
-    dx_dtype = dx_dtype or dy4d.dtype
-    if MBCONV_TORCH:
-        dx = torch.nn.grad.conv2d_input((B, C, H, W), w, dy4d.float().permute(0, 3, 1, 2), stride=stride, padding=1,
-                                        groups=C)
-        return dx.permute(0, 2, 3, 1).contiguous().to(dx_dtype)
-    dx = _se_out(out, (B, H, W, C), dx_dtype, dy4d.device, "dwconv3_bwd_data: out")
-    call("sv_dwconv3_bwd_data", ptr(dy4d), dt(dy4d), ptr(w), ptr(dx), dt(dx), B, H, W, C, stride)
-    return dx
+    return _dwconv_bwd_data(3, dy4d, w, H, W, stride, dx_dtype, out)
 
 
 def dwconv3_bwd_weight(dy4d: torch.Tensor, x4d: torch.Tensor, stride: int, *, dw: torch.Tensor,
                        accumulate: bool = True) -> torch.Tensor:
     """dw [C,1,3,3] f32 (+)= the depthwise weight gradient (per-workgroup partials, folded in part order)."""
-    B, H, W, C = x4d.shape
-    _mb_rows("dwconv3_bwd_weight", C, x4d)
-    _mb_rows("dwconv3_bwd_weight", C, dy4d)
-    _check(stride in (1, 2) and tuple(dy4d.shape) == (B, (H - 1) // stride + 1, (W - 1) // stride + 1, C)
-           and tuple(dw.shape) == (C, 1, 3, 3) and dw.dtype == torch.float32 and dw.is_contiguous(),
-           "dwconv3_bwd_weight: dy [B,OH,OW,C], dw f32 [C,1,3,3]")
-    if MBCONV_TORCH:
-        g = torch.nn.grad.conv2d_weight(x4d.float().permute(0, 3, 1, 2), (C, 1, 3, 3), dy4d.float().permute(0, 3, 1, 2),
-                                        stride=stride, padding=1, groups=C)
-        return dw.add_(g) if accumulate else dw.copy_(g)
-    P = value("sv_dwconv3_bwd_weight_nparts", B, H, W, C, stride)
-    part = torch.empty(P, 9, C, device=x4d.device, dtype=torch.float32)
-    call("sv_dwconv3_bwd_weight", ptr(dy4d), dt(dy4d), ptr(x4d), dt(x4d), ptr(part), ptr(dw), int(accumulate), B, H, W, C,
-         stride)
-    return dw
+    return _dwconv_bwd_weight(3, dy4d, x4d, stride, dw, accumulate)
+
+
+# depthwise 5x5, pad 2 (csrc/dwconv5.hip): the k = 5 blocks of EfficientNet-B0..B4; arguments as the 3x3 wrappers
+def dwconv5_fwd(x4d: torch.Tensor, w: torch.Tensor, stride: int, *, out_dtype=None, out=None) -> torch.Tensor:
+    """Depthwise 5x5, pad 2 -> [B, (H-1)//stride+1, (W-1)//stride+1, C]."""
+    return _dwconv_fwd(5, x4d, w, stride, out_dtype, out)
+
+
+def dwconv5_bwd_data(dy4d: torch.Tensor, w: torch.Tensor, H: int, W: int, stride: int, *, dx_dtype=None,
+                     out=None) -> torch.Tensor:
+    return _dwconv_bwd_data(5, dy4d, w, H, W, stride, dx_dtype, out)
+
+
+def dwconv5_bwd_weight(dy4d: torch.Tensor, x4d: torch.Tensor, stride: int, *, dw: torch.Tensor,
+                       accumulate: bool = True) -> torch.Tensor:
+    """dw [C,1,5,5] f32 (+)= the depthwise weight gradient (per-workgroup partials [P][25][C], folded in part order)."""
+    return _dwconv_bwd_weight(5, dy4d, x4d, stride, dw, accumulate)
 
 
 def _mbse_act(who: str, *ts) -> tuple:

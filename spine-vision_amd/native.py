@@ -277,6 +277,10 @@ _SIGS = {
     "sv_dwconv3_bwd_data": [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_dwconv3_bwd_weight_nparts": [_i32, _i32, _i32, _i32, _i32],
     "sv_dwconv3_bwd_weight": [_p, _i32, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "sv_dwconv5_fwd": [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "sv_dwconv5_bwd_data": [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
+    "sv_dwconv5_bwd_weight_nparts": [_i32, _i32, _i32, _i32, _i32],
+    "sv_dwconv5_bwd_weight": [_p, _i32, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     "sv_mbse_squeeze": [_p, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
     "sv_mbse_excite": [_p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
     "sv_mbse_scale": [_p, _i32, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],

@@ -19,9 +19,11 @@ csrc/mbconv.hip, and the dense 3x3 convolutions of the first stages go through t
 channel stride of the tensors they touch padded to a power of two.  ``swin_tiny`` is built by
 ``backbone.swin.create_swin`` but still raises here: an existing test pins that, and lifting the gate is adding the
 name to ``NATIVE``; ``resnetrs50`` and ``resnet50_d`` are built by ``backbone.resnet.create_resnet`` and raise here for
-the same reason.  Every other name of the reference registry is recognised (``list_backbones`` returns the
-reference's full list) but raises: those (EfficientNet-B0..B4 and MobileNetV3 -- 5x5 depthwise, hard-swish, widths 16 / 40 /
-112 --; and ConvNeXt-xlarge, the other ConvNeXt V2 sizes and ``resnext101``) are outside this build's scope.
+the same reason, and so do ``efficientnet_b0`` .. ``efficientnet_b4``, built by ``backbone.efficientnet.create_efficientnet``
+(5x5 depthwise on csrc/dwconv5.hip, widths 16 / 40 / 112 stored with zero-padded channel strides): the dispatch arm below
+is in place, and lifting the gate is adding the five names to ``NATIVE`` and ``_FEATURE_DIMS``.  Every other name of the
+reference registry is recognised (``list_backbones`` returns the reference's full list) but raises: those (MobileNetV3
+-- hard-swish --; and ConvNeXt-xlarge, the other ConvNeXt V2 sizes and ``resnext101``) are outside this build's scope.
 ``pretrained=True`` cannot download weights offline; pass ``pretrained=False`` or load a timm
 state_dict with ``load_state_dict`` (keys match).
 """
@@ -115,6 +117,10 @@ class BackboneFactory:
             from ...backbone.efficientnet import create_efficientnetv2
 
             model = create_efficientnetv2(name, precision=prec)
+        elif name.startswith("efficientnet_b"):
+            from ...backbone.efficientnet import create_efficientnet
+
+            model = create_efficientnet(name, precision=prec)
         else:
             from ...backbone.resnet import create_resnet
 
